@@ -10,14 +10,16 @@ is captured into ONE HIP graph and replayed (what can overlap inside a forward i
 models).  With N>1 every rank owns its own 64 clouds (weak scaling, no data-path collective) and the per-shard logits
 are all-gathered over RCCL each step.
 
-Rank 0 prints ONE JSON line.  `roofline` describes the hand-written kernel that takes the largest share of the
-step: algorithmic bytes/flops / its average launch duration, measured with HIP events on the
-launch stream in an event-instrumented pass of the same forward.  `cpu_baseline` times the CPU restatement of
-the same forward on the host cores over a bounded sample.  `kernels` lists every hand-written kernel the same way.
-At N=1 the same process then measures the other BASELINE configurations the same way (captured, replayed, timed,
+Rank 0 prints ONE JSON line: `value` (clouds/s) and `ms_per_step` of exactly --steps timed steps after the capture, the settle
+replays and --warmup steps.  That is all a plain run does (plus `--dump-outputs DIR`: the logits of the last timed step as .npy).
+`--full` adds what takes runs of its own: four further timed blocks (`ms_per_step_blocks`), the serial figure, the check of the
+replayed graphs against the eager forward, and `roofline` / `kernels` -- the hand-written kernel that takes the largest share of the
+step: algorithmic bytes/flops / its average launch duration, measured with HIP events on the launch stream in an
+event-instrumented pass of the same forward.  `cpu_baseline` times the CPU restatement of the same forward on the host cores over a
+bounded sample.  At N=1 the same process then measures the other BASELINE configurations the same way (captured, replayed, timed,
 checked against the eager outputs) -> `other_configs`: configs[2] (cls --AS, 10 outliers per cloud), configs[3]
-(pointasnl_sem_seg, 16 x 8192) and the per-GPU share of configs[4] (pointasnl_sem_seg_res, 8 x 10240); and the
-north-star operator sweep -> `ball_query_sweep` (query_ball_point at (B,1024)/(B,512), nsample 32, B = 64..4096).
+(pointasnl_sem_seg, 16 x 8192) and the per-GPU share of configs[4] (pointasnl_sem_seg_res, 8 x 10240); the explicit `modes`;
+and the north-star operator sweep -> `ball_query_sweep` (query_ball_point at (B,1024)/(B,512), nsample 32, B = 64..4096).
 
 Every rank's measurement runs in a worker process under a thin supervisor (`supervise`): the worker reports its phase
 over a pipe, and a job in which a worker makes no progress within the phase's allowance is killed (exact PIDs) instead
@@ -35,15 +37,13 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
-# HIP maps the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4) in creation order, and the forks of a captured
-# forward that land on one queue serialise.  With four queues the mapping that RCCL's own streams leave for the forward is a bad one:
-# the SAME captured step took 1.75-1.80 ms instead of 1.32 once a process group existed -- no collective in the step --, which the
-# driver's N = 2 run would have shown as a 25 % scaling loss.  With three queues every workload runs as with four (cls 1.322 /
-# 1.322, sem_seg 4.39 / 4.37, sem_seg_res 2.376 / 2.376 ms) and RCCL's presence changes nothing (1.32; sem_seg_res 2.375):
-# profiles/r06_hw_queues.txt.  Read by the HIP runtime when it initialises, so main() sets it before torch is imported -- in
-# MULTI-RANK runs only (a plain N = 1 run keeps the runtime's default, under which every number of rounds 1-5 was taken; a value the
-# caller exported wins).  Recorded in config.hip_hw_queues.
-MULTI_RANK_HW_QUEUES = "3"
+# HIP maps the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4), and the forks of a captured forward that
+# land on one queue serialise.  With RCCL started BEFORE the capture, the streams it creates leave the forward a bad mapping: the
+# SAME captured step took 1.75-1.80 ms instead of 1.32 once a process group existed -- no collective in the step --, which the
+# driver's N = 2 run would have shown as a 25 % scaling loss; started and destroyed before the capture it cost nothing (1.32):
+# profiles/r06_hw_queues.txt.  So a multi-rank run captures the main workload's graphs and replays them once before it starts the
+# process group (run_config's on_captured), under the runtime's own queue count, like a plain N = 1 run, and the per-step all-gather
+# is waited for by the forward's stream at once (PASNL_BENCH_GATHER in run_config).  Recorded in config.hip_hw_queues.
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
@@ -647,9 +647,12 @@ def run_config(cfg_index, spec, *a, **kw):
 
 
 def _run_config(cfg_index, spec, steps, warmup, rank=0, world=1, multi=False, graph=True, kernel_pass=True, announce=True,
-                pipeline="serial", extra_blocks=0, _switched=None):
+                pipeline="serial", extra_blocks=0, check=True, keep_last=False, on_captured=None, _switched=None):
     """Measure one workload on the current device -> dict.  The timed region is `steps` forwards bracketed by
     (barrier +) torch.cuda.synchronize() on both sides, max over ranks.
+    check: compare the replayed graphs with the eager forward (`outputs_agree`; None when not checked).  keep_last: return what the
+    last timed step computed (`last_out`, and `last_gathered` on the multi-rank path) as host arrays.  on_captured: called once the
+    graphs are captured and have replayed (main() starts the process group there).
 
     pipeline = "serial": one captured graph per forward, replayed back to back on one stream.
     pipeline = "prefetch": a serving loop over a stream of batches with two input buffers.  The search prefix of a forward
@@ -841,9 +844,20 @@ def _run_config(cfg_index, spec, steps, warmup, rank=0, world=1, multi=False, gr
                 out = forward()
             torch.cuda.current_stream().wait_stream(side)
             graphs, outs = [g], [out]
+        if on_captured is not None:
+            # every graph captured and replayed once (whole rounds over the buffers: buffer 0 is next) BEFORE the caller starts
+            # RCCL: the streams RCCL creates then no longer shift where the forward's branches land among the hardware queues
+            with torch.cuda.stream(side):
+                for g in graphs:
+                    g.replay()
+            torch.cuda.synchronize()
+            on_captured()
         step_no = [0]
 
-        gather_mode = os.environ.get("PASNL_BENCH_GATHER", "async")  # tuning switch: async (default) / sync (round 5's blocking form) / none
+        # tuning switch: sync (default: the forward's stream waits for the step's all-gather -- a stream wait, not a host one) / async
+        # (waited for when its output buffer is reused; under the runtime's four hardware queues the one-rank RCCL path then ran 1.60
+        # ms per step against 1.29 plain, blocking 1.30) / none
+        gather_mode = os.environ.get("PASNL_BENCH_GATHER", "sync")
 
         def step():
             if graphs:
@@ -893,6 +907,9 @@ def _run_config(cfg_index, spec, steps, warmup, rank=0, world=1, multi=False, gr
         if multi:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        if keep_last:  # (before anything else replays the graphs: their output buffers are reused)
+            last_out = last.float().cpu().numpy()
+            last_gathered = gather.out.float().cpu().numpy() if gather is not None else None
         if announce:
             beat("post")
         per_rank_ms = [elapsed / steps * 1e3]
@@ -936,7 +953,7 @@ def _run_config(cfg_index, spec, steps, warmup, rank=0, world=1, multi=False, gr
         # the replayed graphs compute the same function of the same input as the plain eager forward: bit-identical, for every
         # input buffer (prefetch: the last two steps left the outputs of both buffers)
         agree = None
-        if graphs:
+        if graphs and check:
             for i in range(len(graphs)):  # a run of fewer steps than buffers: every graph has to have produced its output once
                 if step_no[0] + i < len(graphs):
                     with torch.cuda.stream(side):
@@ -961,7 +978,7 @@ def _run_config(cfg_index, spec, steps, warmup, rank=0, world=1, multi=False, gr
     return {"B": B, "N": N, "elapsed": elapsed, "block_ms": block_ms, "per_rank_ms": per_rank_ms, "ms_per_step": elapsed / steps * 1e3, "enqueue_ms_per_step": enqueued / steps * 1e3, "clouds_per_s": world * B * steps / elapsed,
             "graph": bool(graphs), "pipeline": pipeline if graphs else "eager", "outputs_agree": agree, "gathered_ok": gathered_ok,
             "shards_differ": shards_differ, "rows": rows, "launch_order": launch_order, "pc": pc, "store": store,
-            "mode_dev": mode_dev}
+            "mode_dev": mode_dev, "last_out": last_out if keep_last else None, "last_gathered": last_gathered if keep_last else None}
 
 
 def ball_query_sweep(batches=(64, 256, 1024, 4096), iters=20):
@@ -1017,6 +1034,24 @@ def median_ms(r):
     """the median over the timed blocks of a run (auxiliary figures: other_configs, modes) -- a single block of ten steps met a
     stalled replay now and then (7.5 / 6.3 / 2.4-ms blocks among 1.4-ms ones, in the canonical-order runs as well), which the median drops"""
     return float(np.median(r["block_ms"]))
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of {name: array} as DIR/<name>.npy, float32.  An array above its share of DUMP_LIMIT_BYTES is
+    written as a fixed sample of its elements: seed 0, flat indices in ascending order, saved beside it as DIR/<name>_index.npy
+    (float64) -- the same sample in every run of the same shape, so that two builds compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, share // (4 + 8), replace=False))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def input_stage_row(iters=10):
@@ -1117,7 +1152,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--proto-shape", choices=["cls", "sem_seg_res"], default="cls", help="--model none: the width of the stand-in logits")
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps each: the first one is `value` (the contract's exactly-K-steps region), all of them go to ms_per_step_blocks")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps steps each: the first one is `value` (the contract's exactly-K-steps region), all of them go to ms_per_step_blocks (default: 1; 5 with --full)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=0, help="clouds per GPU (weak scaling); default: the BASELINE config's")
     ap.add_argument("--AS", action="store_true", help="time configs[2] (adaptive sampling on, noisy clouds) as the main workload")
@@ -1135,8 +1170,15 @@ def main():
                          "of the input level, hand-written kernels only) runs on a side stream of batch k's graph, two input "
                          "buffers (see run_config); the line also carries the serial figure.  serial: one graph per forward, back "
                          "to back")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip `other_configs` and `ball_query_sweep` (they run at N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: further timed blocks, the serial figure, the graph-against-eager "
+                         "check, the per-kernel pass (`kernels`, `roofline`), the CPU baseline, `other_configs`, `modes`, "
+                         "`ball_query_sweep` and `input_stage`.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; rank 0; at "
+                         f"most {DUMP_LIMIT_BYTES >> 20} MB in all, a seeded sample of a larger output), e.g. --dump-outputs bench_out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip `cpu_baseline`")
+    ap.add_argument("--no-others", action="store_true", help="(--full) skip `other_configs` and `ball_query_sweep` (they run at N=1 only)")
     ap.add_argument("--other-steps", type=int, default=10, help="timed steps of each entry of `other_configs`")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the multi-rank code path (RCCL init, per-step all-gather, barriers, max-over-ranks) even with "
@@ -1162,8 +1204,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if (world > 1 or args.force_dist) and args.model != "none":
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", MULTI_RANK_HW_QUEUES)  # (before torch loads the HIP runtime: the comment at the top of the file)
+    full = args.full
+    blocks = args.blocks if args.blocks is not None else (5 if full else 1)
 
     import torch
     import torch.distributed as dist
@@ -1200,6 +1242,7 @@ def main():
     multi = world > 1 or args.force_dist
     allreduce_check = None
     numa_node, cpus_bound = None, 0
+    start_dist = None
     if multi:
         from pointasnl_amd import sharding as _sh
 
@@ -1207,13 +1250,18 @@ def main():
             numa_node, cpus_bound = _sh.bind_to_gpu_numa(local_rank)  # before RCCL starts its proxy thread (it inherits the mask)
         if os.environ.get("PASNL_BENCH_PRECREATE", "1") == "1":
             precreate_streams()
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29531")
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        t = torch.tensor([float(rank + 1)], device="cuda")
-        dist.all_reduce(t)  # sanity: every rank took part in one RCCL all-reduce
-        allreduce_check = float(t.item())
-        assert allreduce_check == world * (world + 1) / 2, allreduce_check
+
+        def start_dist():
+            """RCCL starts once the main workload's graphs are captured and have replayed (run_config's on_captured): see
+            the comment at the top of the file"""
+            nonlocal allreduce_check
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            os.environ.setdefault("MASTER_PORT", "29531")
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+            t = torch.tensor([float(rank + 1)], device="cuda")
+            dist.all_reduce(t)  # sanity: every rank took part in one RCCL all-reduce
+            allreduce_check = float(t.item())
+            assert allreduce_check == world * (world + 1) / 2, allreduce_check
 
     main_index = {"cls": 2 if args.AS else 1, "sem_seg": 3, "sem_seg_res": 4}[args.model]
     spec = dict(WORKLOADS[main_index])
@@ -1224,9 +1272,15 @@ def main():
     if args.points:
         spec["points"] = args.points
     res = run_config(main_index, spec, args.steps, args.warmup, rank=rank, world=world, multi=multi, graph=not args.no_graph,
-                     pipeline=args.pipeline, extra_blocks=max(0, args.blocks - 1))
+                     pipeline=args.pipeline, extra_blocks=max(0, blocks - 1), kernel_pass=full or args.launch_order, check=full,
+                     keep_last=args.dump_outputs is not None, on_captured=start_dist)
+    if args.dump_outputs is not None and rank == 0:  # what a caller of the timed path receives from its last step
+        dumped = {"logits": res["last_out"]}
+        if world > 1:
+            dumped["gathered_logits"] = res["last_gathered"]
+        dump_outputs(args.dump_outputs, dumped)
     serial = None
-    if args.pipeline != "serial" and not args.no_graph:  # the same workload without the cross-batch overlap (every rank takes part)
+    if full and args.pipeline != "serial" and not args.no_graph:  # the same workload without the cross-batch overlap (every rank takes part)
         # (an auxiliary figure: the better of two short runs, so that one stalled replay -- a clock ramp, an allocator sync --
         # does not pass for the serial step time)
         r0 = min((run_config(main_index, spec, min(args.steps, 20), 3, rank=rank, world=world, multi=multi, graph=True,
@@ -1242,12 +1296,12 @@ def main():
 
     rows = res["rows"]
     cpu = None
-    if not args.no_cpu_baseline and args.model == "cls" and world == 1:  # rank 0 at N=1 only
+    if full and not args.no_cpu_baseline and args.model == "cls" and world == 1:  # rank 0 at N=1 only
         cpu = cpu_baseline(res["pc"], res["store"].export_numpy(), spec["AS"])
         beat("post")
 
     others, sweep, sweep_traffic_source, modes, input_stage = None, None, None, None, None
-    if world == 1 and not args.no_others and not args.force_dist:
+    if full and world == 1 and not args.no_others and not args.force_dist:
         others = []
         for ci, ospec in WORKLOADS.items():
             if ci == main_index:
@@ -1351,8 +1405,8 @@ def main():
         "config": config,
         "roofline": roofline_of(rows),
         "cpu_baseline": cpu,
-        "handwritten_kernel_us_per_step": round(sum(r["avg_us"] * r["launches"] for r in rows) / max(1, min(args.steps, 20)), 1),
-        "kernels": rows,
+        "handwritten_kernel_us_per_step": round(sum(r["avg_us"] * r["launches"] for r in rows) / max(1, min(args.steps, 20)), 1) if full else None,
+        "kernels": rows if full else None,
         "other_configs": others,
         "modes": modes,
         "ball_traffic_source": sweep_traffic_source,

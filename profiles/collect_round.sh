@@ -10,12 +10,12 @@ TAG=${1:-r03}
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 O=gpurun_out
-python bench.py --steps 50 --warmup 10 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python bench.py --steps 50 --warmup 10 --pipeline serial --no-cpu-baseline > $O/${TAG}_bench_serial.json 2>> $O/${TAG}_bench.err
+python bench.py --steps 50 --warmup 10 --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --steps 50 --warmup 10 --full --pipeline serial --no-cpu-baseline > $O/${TAG}_bench_serial.json 2>> $O/${TAG}_bench.err
 for cfg in "cls_b64:" "cls_AS_b64:--AS" "sem_seg_b16:--model sem_seg" "sem_seg_res_b8:--model sem_seg_res"; do
   name=${cfg%%:*}; flags=${cfg#*:}
   rm -rf $O/prof_$name
-  timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$name -o p -f csv -- python bench.py --worker --steps 20 --warmup 5 --no-cpu-baseline --no-others $flags > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$name -o p -f csv -- python bench.py --worker --steps 20 --warmup 5 --full --no-cpu-baseline --no-others $flags > /dev/null 2>&1
   cp $O/prof_$name/p_kernel_stats.csv $O/${TAG}_${name}_kernel_stats.csv 2>/dev/null
 done
 bash profiles/collect_mfma_util.sh > $O/${TAG}_mfma_util.log 2>&1; cp $O/mfma_util.json $O/${TAG}_mfma_util.json 2>/dev/null

@@ -165,3 +165,20 @@ def test_asm_scan_checks_wait_states_in_front_of_inline_dpp():
 	;;#ASMEND
 """.split("\n")
     assert asm_scan.asm_mfma_hazards(good, 0, len(good)) == []
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: a small array is written whole; one above its share of the limit as the same seeded sample of its elements
+    in every run, with the flat indices beside it, and all files together stay within the limit."""
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 16)
+    small = np.arange(64 * 40, dtype=np.float64).reshape(64, 40)
+    big = np.random.default_rng(1).standard_normal((8, 4096)).astype(np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"logits": small, "big": big})
+    got = np.load(tmp_path / "a" / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 40) and np.array_equal(got, small.astype(np.float32))
+    idx = np.load(tmp_path / "a" / "big_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), big.reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "big_index.npy"))
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "a").iterdir()) <= 1 << 16  # (128: the .npy header)

@@ -6,6 +6,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,6 +102,23 @@ def test_refuses_instead_of_degrading():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps, nothing of --full in the line, and --dump-outputs leaves the logits the
+    last timed step computed -- the same file from two runs with the same arguments."""
+    lines = []
+    for d in ("a", "b"):
+        p = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d), timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "point-clouds/s" and line["dtype"] == "f32" and len(line["ms_per_step_blocks"]["blocks"]) == 1
+    assert line["kernels"] is None and line["cpu_baseline"] is None and line["other_configs"] is None and line["serial"] is None
+    a, b = (np.load(tmp_path / d / "logits.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (64, 40) and np.isfinite(a).all() and np.array_equal(a, b)
+
+
+@pytest.mark.gpu
 def test_stalled_run_is_killed_not_hung():
     """The worker hangs in the watched region (test hook); the supervisor kills it (exact PID), prints no JSON line and
     exits with code 3 long before the worker's own sleep would end."""
@@ -117,7 +135,7 @@ def test_stalled_run_is_killed_not_hung():
 def test_rccl_path_with_one_rank():
     """Everything of the multi-rank path but the wire, on one GPU: RCCL init, the all-reduce check, the per-step
     all-gather of the logits (captured forward + collective on the same stream), barriers, max-over-ranks timing."""
-    p = _bench("--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", timeout=900)
+    p = _bench("--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     cfg = line["config"]
@@ -130,7 +148,8 @@ def test_rccl_path_sem_seg_res_gather_is_asynchronous():
     """configs[4] on the multi-rank path with one rank: the per-step all-gather moves the (8, 10240 x 20) segmentation logits
     (6.5 MB per rank, not the 10 KB of the classifier) behind the replayed graph, and the host only ENQUEUES a step: issuing
     the steps takes a fraction of the time the GPU needs for them, so there is no host synchronisation inside a step."""
-    p = _bench("--gpus", "1", "--force-dist", "--model", "sem_seg_res", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", timeout=900)
+    p = _bench("--gpus", "1", "--force-dist", "--model", "sem_seg_res", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline",
+               timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     cfg = line["config"]
@@ -186,8 +205,8 @@ def test_eight_ranks_protocol_line_carries_every_multi_rank_key(shape, width):
 def test_one_rank_through_the_multi_rank_path_agrees_with_the_plain_line():
     """--gpus 1 --force-dist (RCCL init, per-step all-gather, barriers, max-over-ranks) against the plain N = 1 line of the same
     process layout: within 2 %, so that the first SCALE record is comparable with BENCH by construction."""
-    a = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-others", timeout=900)
-    b = _bench("--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-others", timeout=900)
+    a = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-others", timeout=900)
+    b = _bench("--gpus", "1", "--force-dist", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-others", timeout=900)
     assert a.returncode == 0 and b.returncode == 0, (a.stderr[-1500:], b.stderr[-1500:])
     la = json.loads([l for l in a.stdout.splitlines() if l.startswith("{")][-1])
     lb = json.loads([l for l in b.stdout.splitlines() if l.startswith("{")][-1])
