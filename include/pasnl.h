@@ -291,6 +291,25 @@ int pasnl_sa_cell_centre0(int b, int n, int c, int m, int k, int c1, int c2, con
                           const float* ww, const float* bw, float* out, float* skip_max, float* new_xyz, float* new_feature,
                           pasnl_stream_t stream);
 
+/* The pre-projected form of pasnl_sa_cell for layers whose groups gather each source point many times.  conv0 is linear before
+ * its ReLU: [xyz - centre | xyz | feature] . w0 + b0 = (xyz - centre) . w0[0:3] + proj, where
+ *   pasnl_sa_project: proj (b,n,c1) = [xyz | feature] . w0[3:6+c] + b0, once per source point (replaces the per-neighbour
+ *   products of those 3 + c rows of w0 inside the cell);
+ *   pasnl_sa_cell_pre / pasnl_sa_cell_pre_centre0: pasnl_sa_cell / pasnl_sa_cell_centre0 with conv0 = proj[b, idx] +
+ *   (xyz - centre) . w0[0:3] (only those 3 rows of w0 are read; b0 is in proj).  skip_max bit-equal to pasnl_sa_cell's; out
+ *   within fp32 rounding of it (conv0 sums in another order).
+ * c1 = c2 in {32, 64, 128} (c1 = the width of proj); c % 4 == 0 with 16-byte aligned feature and proj, else PASNL_EUNSUPPORTED;
+ * other limits as pasnl_sa_cell / pasnl_sa_cell_centre0. */
+int pasnl_sa_project(int b, int n, int c, int c1, const float* xyz, const float* feature, const float* w0, const float* b0,
+                     float* proj, pasnl_stream_t stream);
+int pasnl_sa_cell_pre(int b, int n, int c, int m, int k, int c1, int c2, const float* xyz, const float* feature,
+                      const float* proj, const int* idx, const float* new_xyz, const float* w0, const float* w1, const float* b1,
+                      const float* ww, const float* bw, float* out, float* skip_max, pasnl_stream_t stream);
+int pasnl_sa_cell_pre_centre0(int b, int n, int c, int m, int k, int c1, int c2, const float* xyz, const float* feature,
+                              const float* proj, const int* idx, const float* w0, const float* w1, const float* b1,
+                              const float* ww, const float* bw, float* out, float* skip_max, float* new_xyz, float* new_feature,
+                              pasnl_stream_t stream);
+
 /* pasnl_sa_cell / pasnl_sa_cell_centre0 (new_xyz == NULL: the centres are neighbour 0 and new_xyz_out / new_feature_out are
  * written, else both are ignored) that ALSO get the feature rows of w0 (rows 6 .. 5 + c) and w1 in the matrix instruction's
  * operand order -- pasnl_mlp3_pack_weights(c, c1, w0 + 6 * c1, w0_features_packed) and pasnl_mlp3_pack_weights(c1, c2, w1,

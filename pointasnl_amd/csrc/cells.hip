@@ -911,6 +911,7 @@ struct SaGatherSrc {
   int centre0;           // 1: the centre of a group is its neighbour 0, xyz[b, idx[b,j,0]] (AdaptiveSampling with no neighbours)
   float* new_xyz_out;    // centre0 only, optional: (b,m,3) the centres, and
   float* new_feature_out;  //                          (b,m,3+c) [centre | feature row of neighbour 0]  (pasnl_take_neighbor0's outputs)
+  const float* proj;     // PRE only: (b,n,c1) = pasnl_sa_project's table, conv0 of every source point without its centred columns
 };
 
 template <int C1, int C2>
@@ -1074,19 +1075,26 @@ constexpr int SA_SKIP_REP = 4;
 
 // SINGLE: the layer has ONE convolution (mlp = [c, c]): conv0 is formed with its operands swapped -- H1 = X . W0 with rows =
 // neighbours, the layout the matmul takes as conv1's output -- and there is no conv1 (w1 / b1 are not read)
-template <int C1, int C2, int NW, bool VEC, bool TAIL8, bool XYZ3 = false, bool SINGLE = false>  // XYZ3: the feature rows are 3 wide (xyz-only first layers)
+// PRE (pasnl_sa_cell_pre): conv0 is linear before its ReLU, so X . W0 = (xyz - c) . W0[0:3] + [xyz | 1 | feature] . W0[3:] and the
+// second term depends on the source point only.  pasnl_sa_project tabulates it once per point (src.proj); the cell gathers a
+// tile's rows of that table straight into the conv0 accumulators (16-byte loads: a lane's 16 rows kappa(r, h) of a 32-channel
+// block are four runs of 4 channels) and adds the centred coordinates with TWO MFMA steps (columns x-cx, y-cy | z-cz, 0; their
+// weights live in registers) instead of the row's 4 + c/2 steps.  W0 does not go into LDS.  The skip maxima still need the raw
+// rows: chunk 0 comes with the tile's coordinates as before, chunks 1.. are loaded and folded with ds_max during conv1.
+template <int C1, int C2, int NW, bool VEC, bool TAIL8, bool XYZ3 = false, bool SINGLE = false, bool PRE = false>  // XYZ3: the feature rows are 3 wide (xyz-only first layers)
 __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, int w, SaGatherSrc src,
                                                          const float* __restrict__ w0, const float* __restrict__ b0,
                                                          const float* __restrict__ w1, const float* __restrict__ b1,
                                                          const float* __restrict__ ww, const float* __restrict__ bw,
                                                          float* __restrict__ out) {
+  static_assert(!PRE || (VEC && !XYZ3 && !SINGLE), "the pre-projected form takes 16-byte rows and two convolutions");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SA_PROBE(unsigned long long pentry; SA_MARK0(pentry);)
   const int cf = w - 6;
   const int wi = 8 + cf;                            // internal width
   const int wp = (wi + 31) & ~31;
-  float* W0s = reinterpret_cast<float*>(smem);      // [wp][C1], rows in internal column order
-  float* W1s = W0s + (size_t)wp * C1;               // [C1][C2]
+  float* W0s = reinterpret_cast<float*>(smem);      // [wp][C1], rows in internal column order (PRE: none)
+  float* W1s = W0s + (PRE ? 0 : (size_t)wp * C1);   // [C1][C2]
   float* Wws = W1s + C1 * C2;                       // [3 steps][2 halves][32]: weight net, zero rows for the unused half
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in an SGPR: the group bookkeeping below is scalar work
@@ -1103,7 +1111,7 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
   constexpr int T = NW * 64;
   if (((reinterpret_cast<uintptr_t>(w0) | reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(b0)) & 15) == 0) {
     constexpr int Q = C1 / 4, SB = 8;
-    const int n0 = wp * Q;  // float4 items of W0s; row r of W0s = w0 row r (r < 6) | b0 (6) | 0 (7) | w0 row r - 2 | 0 (r >= wi)
+    const int n0 = PRE ? 0 : wp * Q;  // float4 items of W0s; row r of W0s = w0 row r (r < 6) | b0 (6) | 0 (7) | w0 row r - 2 | 0 (r >= wi)
     for (int base = tid; base < n0; base += SB * T) {
       float4 v[SB];
 #pragma unroll
@@ -1127,7 +1135,7 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         if (base + u * T < N1) reinterpret_cast<float4*>(W1s)[base + u * T] = v[u];
     }
   } else {
-    for (int i = tid; i < wp * C1; i += T) {
+    for (int i = tid; i < (PRE ? 0 : wp * C1); i += T) {
       const int r = i / C1, c1 = i - r * C1;
       float v = 0.f;
       if (r < 6) v = w0[(size_t)r * C1 + c1];
@@ -1154,6 +1162,14 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
   const float bwr = bw[ql];
   const int nchunk = wp / 32;
   const int cf4 = cf >> 2;
+  // PRE: W0's rows for the centred coordinates; step s contracts column 2s + h (x - cx, y - cy | z - cz, a zero column)
+  float w0c[2][C1 / 32];
+  if constexpr (PRE) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int ob = 0; ob < C1 / 32; ++ob) w0c[s][ob] = 2 * s + h < 3 ? w0[(size_t)(2 * s + h) * C1 + ob * 32 + ql] : 0.f;
+  }
 
   // XCD-aware work distribution: workgroup i runs on XCD i % 8 (round-robin dispatch) and every XCD has its own
   // 4 MiB L2, so XCD x is given whole clouds (x, x+8, ...): the tables it gathers from (8 clouds x <= 270 KiB at
@@ -1184,6 +1200,8 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
   unsigned frow_off = 0;                 // and its feature row: element offset into src.feature (one register, not a 64-bit
   const float* const fbase_ = src.feature;  // pointer per lane; a tensor of < 2^32 floats: sa_cell_entry checks)
 #define frow (fbase_ + frow_off)
+  f32x16 pn[PRE ? C1 / 32 : 1];          // PRE: the tile row's pre-projected conv0 (rows kappa(r, h) of each 32-channel block)
+  float xs[16];                          // PRE: a chunk of the current tile's rows, for the skip maxima only
   // operands [u0, u1) of chunk ch (VEC: whole 16-byte groups); the loops unroll, u0 / u1 are constants at every call
   auto load_part = [&](int ch, int u0, int u1) {
     if constexpr ((PASNL_SA_ABLATE & 2) != 0) {
@@ -1234,6 +1252,31 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       if (TAIL8 && wi < 32) load_part(0, 0, 8);  // a one-chunk row: only 8 steps exist
       else load_part(0, 0, 16);
     }
+    if constexpr (PRE) {
+      const float4* pr = reinterpret_cast<const float4*>(src.proj) + ((size_t)bc * src.n + i) * (C1 / 4) + h;
+#pragma unroll
+      for (int ob = 0; ob < C1 / 32; ++ob)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 t4 = pr[ob * 8 + 2 * q];  // channels ob*32 + 8q + 4h .. +4 = rows kappa(4q .. 4q+3, h)
+          pn[ob][4 * q] = t4.x; pn[ob][4 * q + 1] = t4.y; pn[ob][4 * q + 2] = t4.z; pn[ob][4 * q + 3] = t4.w;
+        }
+    }
+  };
+  // PRE: chunk ch of the row at feature offset off into xs (the columns past the row's width are never read: unmasked)
+  auto load_skip = [&](int ch, unsigned off) {
+    const int g0 = ch * 8 + 4 * h - 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 t4 = reinterpret_cast<const float4*>(fbase_ + off)[min(max(g0 + q, 0), cf4 - 1)];
+      xs[4 * q] = t4.x; xs[4 * q + 1] = t4.y; xs[4 * q + 2] = t4.z; xs[4 * q + 3] = t4.w;
+    }
+  };
+  auto fold_skip = [&](int ch, const float (&v)[16]) {
+    typedef __attribute__((address_space(3))) float lds_float;
+    lds_float* srow = (lds_float*)(skl + ch * 32);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) __hip_atomic_fetch_max(srow + t, v[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
   };
   // Software pipeline over tiles: the neighbour indices of tile t+1 are requested when tile t starts, its rows when
   // tile t has finished conv0; the centre of the next group when a group starts.  Only a wave's first tile waits
@@ -1287,13 +1330,15 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       SA_PROBE(a_start += pt1 - pt0;)
 
       f32x16 H1T[C1 / 32];
+      if constexpr (!PRE) {  // (PRE: the first conv0 step writes H1T from the gathered table rows)
 #pragma unroll
       for (int ob = 0; ob < C1 / 32; ++ob)
 #pragma unroll
         for (int r = 0; r < 16; ++r) H1T[ob][r] = 0.f;
+      }
       // (pinned in AccVGPRs where registers are scarce; the narrow first-layer variant has room, and without the pin the
       // compiler folds the zeros into the first MFMA's accumulator operand instead of writing 16 registers per block)
-      if constexpr (!XYZ3) {
+      if constexpr (!XYZ3 && !PRE) {
 #pragma unroll
         for (int ob = 0; ob < C1 / 32; ++ob) asm volatile("" : "+a"(H1T[ob]));
       }
@@ -1341,6 +1386,18 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
 #pragma unroll
       for (int t = 0; t < (VEC ? 3 : 2); ++t)
         G = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[t], Wws[(t * 2 + h) * 32 + ql], G, 0, 0, 0);
+
+      // the feature row of THIS tile (PRE: its chunks 1.. are read during conv1, after the next tile's rows were requested)
+      [[maybe_unused]] const unsigned fcur = frow_off;
+      if constexpr (PRE) {
+        // conv0 = the table rows + (xyz - c) . W0[0:3]: two steps, accumulated onto the gathered rows
+        const float d0 = h ? py - cy : px - cx, d1 = h ? 0.f : pz - cz;
+#pragma unroll
+        for (int ob = 0; ob < C1 / 32; ++ob) H1T[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0c[0][ob], d0, pn[ob], 0, 0, 0);
+#pragma unroll
+        for (int ob = 0; ob < C1 / 32; ++ob) H1T[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0c[1][ob], d1, H1T[ob], 0, 0, 0);
+        fold_skip(0, xr);
+      } else {  // (not re-indented: the plain form's conv0 over the whole row, chunk by chunk)
 
       constexpr int RS = VEC ? 1 : 2;  // W0 row / column stride between consecutive MFMA steps
       // Skip connection: the column maxima over the group's rows.  The fp32 MFMA runs on the SIMD's vector lanes, so
@@ -1444,8 +1501,10 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         if (live <= 8) chunk_steps(ch, std::integral_constant<int, 8>{}, std::false_type{});
         else chunk_steps(ch, std::integral_constant<int, 16>{}, std::false_type{});
       }
-      // rows of the following tile (same group, or the first tile of the next one): they arrive during conv1
-      request_rows(tile + 32 < ktile ? bi : bi_next, inext);
+      }  // !PRE
+      // rows of the following tile (same group, or the first tile of the next one): they arrive during conv1.  (PRE: after
+      // conv1's first block -- conv0's two steps would not cover the wait for the indices requested at the top of the tile)
+      if constexpr (!PRE) request_rows(tile + 32 < ktile ? bi : bi_next, inext);
       SA_MARK(pt2);
       SA_PROBE(a_conv0 += pt2 - pt1;)
       // ReLU (the bias came with the MFMA); G: bias + ReLU
@@ -1473,6 +1532,9 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       } else
 #pragma unroll
       for (int cb = 0; cb < C2 / 32; ++cb) {
+        // PRE: chunk 1 + cb of this tile's rows for the skip maxima, folded behind the block's products (the last chunk again
+        // where the row has fewer: a maximum taken twice is the same maximum)
+        if constexpr (PRE) load_skip(min(1 + cb, nchunk - 1), fcur);
         f32x16 H2;
 #pragma unroll
         for (int r = 0; r < 16; ++r) H2[r] = 0.f;
@@ -1497,6 +1559,16 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         for (int r = 0; r < 16; ++r) H2[r] = fmaxf(H2[r] + b1r[cb], 0.f);
 #pragma unroll
         for (int t = 0; t < 16; ++t) M[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(H2[t], G[t], M[cb], 0, 0, 0);
+        if constexpr (PRE) {
+          if (cb == 0) request_rows(tile + 32 < ktile ? bi : bi_next, inext);  // (see above: they arrive during blocks 1..)
+          if (nchunk > 1) fold_skip(min(1 + cb, nchunk - 1), xs);
+        }
+      }
+      if constexpr (PRE) {
+        for (int ch = 1 + C2 / 32; ch < nchunk; ++ch) {  // rows wider than the blocks: the remaining chunks one by one
+          load_skip(ch, fcur);
+          fold_skip(ch, xs);
+        }
       }
       if (src.centre0 && tile == 0 && src.new_feature_out) {
         float* nfo = src.new_feature_out + (size_t)g * (3 + cf);
@@ -2530,13 +2602,13 @@ static int local_cell_dispatch(long groups, int k, int w, int c1, int c2, const 
   return PASNL_EUNSUPPORTED;
 }
 
-template <int C1, int C2, int NW, bool VEC, bool TAIL8, bool XYZ3 = false, bool SINGLE = false>
+template <int C1, int C2, int NW, bool VEC, bool TAIL8, bool XYZ3 = false, bool SINGLE = false, bool PRE = false>
 static int sa_cell_launch(long groups, int k, int w, SaGatherSrc src, const float* w0, const float* b0, const float* w1,
                           const float* b1, const float* ww, const float* bw, float* out, hipStream_t st) {
   const int wp = (8 + (w - 6) + 31) & ~31;  // internal width: [xyz-c | xyz | 1 | 0 | feature], padded to 32-chunks
-  size_t lds = ((size_t)wp * C1 + (size_t)C1 * C2 + 6 * 32 + (size_t)NW * SA_SKIP_REP * (wp + 4)) * sizeof(float);
+  size_t lds = ((PRE ? 0 : (size_t)wp * C1) + (size_t)C1 * C2 + 6 * 32 + (size_t)NW * SA_SKIP_REP * (wp + 4)) * sizeof(float);
   if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
-  auto kern = sa_cell_kernel<C1, C2, NW, VEC, TAIL8, XYZ3, SINGLE>;
+  auto kern = sa_cell_kernel<C1, C2, NW, VEC, TAIL8, XYZ3, SINGLE, PRE>;
   if (lds > 48 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return PASNL_ELAUNCH;
@@ -3006,6 +3078,188 @@ extern "C" int pasnl_sa_cell_centre0(int b, int n, int c, int m, int k, int c1, 
   PASNL_REQUIRE((long)b * m == 0 || (new_xyz && new_feature), PASNL_ENULL);
   return sa_cell_entry(b, n, c, m, k, c1, c2, xyz, feature, idx, nullptr, w0, b0, w1, b1, ww, bw, out, skip_max, new_xyz,
                        new_feature, stream);
+}
+
+// =============================================================================================
+// The pre-projected cell (sa_cell_kernel with PRE) and its table.  A layer whose groups gather every source point many
+// times (cls layer2: 128 centres x 64 neighbours over 512 points = 16 times) spends most of conv0 recomputing the same
+// products: P[b,i] = [xyz_i | 1 | feature_i] . [W0[3:6]; b0; W0[6:]] is formed here ONCE per point, and the cell adds the
+// centred coordinates' 3 columns.  Operands as in sa_cell_kernel: internal columns [0 0 0 | xyz | 1 | 0 | feature] (the
+// centred coordinates zero), 16-byte loads, one wave = 32 points, D = P^T (rows = channels, columns = points) -- lane (ql, h)
+// holds point ql's channels ob*32 + kappa(r, h), stored as four 16-byte runs per block.  The weights sit in LDS in the
+// cell's internal row order (rows 0..2 zero).
+// =============================================================================================
+template <int C1>
+__global__ __launch_bounds__(256) void sa_project_kernel(int rows, int cf, const float* __restrict__ xyz,
+                                                         const float* __restrict__ feature, const float* __restrict__ w0,
+                                                         const float* __restrict__ b0, float* __restrict__ proj) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* Ws = reinterpret_cast<float*>(smem);  // [wp][C1]
+  const int wi = 8 + cf, wp = (wi + 31) & ~31, nchunk = wp / 32, cf4 = cf >> 2;
+  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, ql = lane & 31;
+  if (((reinterpret_cast<uintptr_t>(w0) | reinterpret_cast<uintptr_t>(b0)) & 15) == 0) {
+    // 16-byte loads, SB in flight per thread before the first LDS store (a dependent dword load + store per iteration made
+    // the copy of 80 KiB the larger part of the launch)
+    constexpr int Q = C1 / 4, SB = 8;
+    const int n4 = wp * Q;
+    for (int base = tid; base < n4; base += SB * 256) {
+      float4 v[SB];
+#pragma unroll
+      for (int u = 0; u < SB; ++u) {
+        const int i = min(base + u * 256, n4 - 1), r = i / Q, q = i - r * Q;
+        const float* srow = r == 6 ? b0 : w0 + (size_t)(r < 6 ? r : min(max(r, 8), wi - 1) - 2) * C1;
+        v[u] = reinterpret_cast<const float4*>(srow)[q];
+        if (r < 3 || r == 7 || r >= wi) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int u = 0; u < SB; ++u)
+        if (base + u * 256 < n4) reinterpret_cast<float4*>(Ws)[base + u * 256] = v[u];
+    }
+  } else {
+    for (int i = tid; i < wp * C1; i += 256) {
+      const int r = i / C1, c1 = i - r * C1;
+      float v = 0.f;
+      if (r >= 3 && r < 6) v = w0[(size_t)r * C1 + c1];
+      else if (r == 6) v = b0[c1];
+      else if (r >= 8 && r < wi) v = w0[(size_t)(r - 2) * C1 + c1];
+      Ws[i] = v;
+    }
+  }
+  __syncthreads();
+  const int row0 = (blockIdx.x * 4 + (tid >> 6)) * 32;
+  if (row0 >= rows) return;
+  const int row = min(row0 + ql, rows - 1);
+  const float4* frow4 = reinterpret_cast<const float4*>(feature + (size_t)row * cf);
+  const float px = xyz[(size_t)row * 3], py = xyz[(size_t)row * 3 + 1], pz = xyz[(size_t)row * 3 + 2];
+  f32x16 acc[C1 / 32];
+#pragma unroll
+  for (int ob = 0; ob < C1 / 32; ++ob)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[ob][r] = 0.f;
+  // step t contracts column ch*32 + t (lanes 0..31) and ch*32 + 16 + t (lanes 32..63): this lane's 16 columns.  The next
+  // chunk's are requested before the current one's products (clamped chunk index: the last request is a dummy)
+  float xr[16], xn[16];
+  auto load = [&](int ch, float (&v)[16]) {
+    const int g0 = ch * 8 + 4 * h - 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 t4 = frow4[min(max(g0 + q, 0), cf4 - 1)];
+      v[4 * q] = t4.x; v[4 * q + 1] = t4.y; v[4 * q + 2] = t4.z; v[4 * q + 3] = t4.w;
+    }
+  };
+  load(0, xn);
+  for (int ch = 0; ch < nchunk; ++ch) {
+    const int g0 = ch * 8 + 4 * h - 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool ok = g0 + q >= 0 && g0 + q < cf4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xr[4 * q + e] = ok ? xn[4 * q + e] : 0.f;
+    }
+    load(min(ch + 1, nchunk - 1), xn);
+    if (ch == 0 && h == 0) {
+      xr[0] = 0.f; xr[1] = 0.f; xr[2] = 0.f; xr[3] = px;
+      xr[4] = py; xr[5] = pz; xr[6] = 1.f; xr[7] = 0.f;
+    }
+    const float* wb = Ws + (size_t)(ch * 32 + 16 * h) * C1 + ql;
+#pragma unroll
+    for (int t = 0; t < 16; ++t)
+#pragma unroll
+      for (int ob = 0; ob < C1 / 32; ++ob)
+        acc[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(size_t)t * C1 + ob * 32], xr[t], acc[ob], 0, 0, 0);
+  }
+  if (row0 + ql < rows) {
+    float4* o = reinterpret_cast<float4*>(proj + (size_t)(row0 + ql) * C1) + h;
+#pragma unroll
+    for (int ob = 0; ob < C1 / 32; ++ob)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        o[ob * 8 + 2 * q] = make_float4(acc[ob][4 * q], acc[ob][4 * q + 1], acc[ob][4 * q + 2], acc[ob][4 * q + 3]);
+  }
+}
+
+template <int C1>
+static int sa_project_launch(int rows, int cf, const float* xyz, const float* feature, const float* w0, const float* b0,
+                             float* proj, hipStream_t st) {
+  const int wp = (8 + cf + 31) & ~31;
+  const size_t lds = (size_t)wp * C1 * sizeof(float);
+  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
+  auto kern = sa_project_kernel<C1>;
+  if (lds > 48 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return PASNL_ELAUNCH;
+  const long tiles = (rows + 31) / 32;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((tiles + 3) / 4)), dim3(256), lds, st, rows, cf, xyz, feature, w0, b0, proj);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_sa_project(int b, int n, int c, int c1, const float* xyz, const float* feature, const float* w0,
+                                const float* b0, float* proj, pasnl_stream_t stream) {
+  PASNL_REQUIRE(b >= 0 && n > 0 && c > 0 && c1 > 0, PASNL_EINVAL);
+  PASNL_REQUIRE((long)b * n < (1L << 31) - 32, PASNL_EUNSUPPORTED);
+  if ((long)b * n == 0) return PASNL_OK;
+  PASNL_REQUIRE(xyz && feature && w0 && b0 && proj, PASNL_ENULL);
+  PASNL_REQUIRE(c % 4 == 0 && reinterpret_cast<uintptr_t>(feature) % 16 == 0 && reinterpret_cast<uintptr_t>(proj) % 16 == 0,
+                PASNL_EUNSUPPORTED);
+  hipStream_t st = pasnl_hip_stream(stream);
+  const int rows = b * n;
+  if (c1 == 32) return sa_project_launch<32>(rows, c, xyz, feature, w0, b0, proj, st);
+  if (c1 == 64) return sa_project_launch<64>(rows, c, xyz, feature, w0, b0, proj, st);
+  if (c1 == 128) return sa_project_launch<128>(rows, c, xyz, feature, w0, b0, proj, st);
+  return PASNL_EUNSUPPORTED;
+}
+
+// Waves per workgroup: two per SIMD at c1 = 32; from c1 = 64 up the next tile's table rows in flight need more than the 256
+// registers two waves leave each (c1 = 64 at 8 waves: 35 spilled registers).  The occupancy query in sa_cell_launch sizes the
+// grid (without W0 the 128-channel cell's LDS holds 75 KiB instead of 155, but its 438 registers keep it at one wave per SIMD).
+template <int C1, int C2>
+static int sa_cell_pre_cfg(long groups, int k, int w, SaGatherSrc src, const float* w0, const float* w1, const float* b1,
+                           const float* ww, const float* bw, float* out, hipStream_t st) {
+  constexpr int NW = C1 >= 64 ? 4 : 8;
+  return sa_cell_launch<C1, C2, NW, true, false, false, false, true>(groups, k, w, src, w0, nullptr, w1, b1, ww, bw, out, st);
+}
+
+static int sa_cell_pre_entry(int b, int n, int c, int m, int k, int c1, int c2, const float* xyz, const float* feature,
+                             const float* proj, const int* idx, const float* new_xyz, const float* w0, const float* w1,
+                             const float* b1, const float* ww, const float* bw, float* out, float* skip_max, float* new_xyz_out,
+                             float* new_feature_out, pasnl_stream_t stream) {
+  PASNL_REQUIRE(b >= 0 && n > 0 && c > 0 && m >= 0 && k > 0 && c1 > 0 && c2 > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(k % 32 == 0, PASNL_EUNSUPPORTED);
+  const long groups = (long)b * m;
+  if (groups == 0) return PASNL_OK;
+  PASNL_REQUIRE(groups < (1L << 31), PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE((long)b * n * c < (1L << 32), PASNL_EUNSUPPORTED);  // feature rows are addressed by 32-bit element offsets
+  PASNL_REQUIRE(xyz && feature && proj && idx && w0 && w1 && b1 && ww && bw && out && skip_max, PASNL_ENULL);
+  PASNL_REQUIRE(new_xyz || m <= n, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(!new_feature_out || c <= 128, PASNL_EUNSUPPORTED);  // two words per lane carry neighbour 0's row
+  // 16-byte rows: feature and table
+  PASNL_REQUIRE(c % 4 == 0 && reinterpret_cast<uintptr_t>(feature) % 16 == 0 && reinterpret_cast<uintptr_t>(proj) % 16 == 0,
+                PASNL_EUNSUPPORTED);
+  SaGatherSrc src{xyz, feature, idx, new_xyz ? new_xyz : xyz, skip_max, n, m, new_xyz ? 0 : 1, new_xyz_out, new_feature_out, proj};
+  hipStream_t st = pasnl_hip_stream(stream);
+  const int w = 6 + c;
+  if (c1 == 32 && c2 == 32) return sa_cell_pre_cfg<32, 32>(groups, k, w, src, w0, w1, b1, ww, bw, out, st);
+  if (c1 == 64 && c2 == 64) return sa_cell_pre_cfg<64, 64>(groups, k, w, src, w0, w1, b1, ww, bw, out, st);
+  if (c1 == 128 && c2 == 128) return sa_cell_pre_cfg<128, 128>(groups, k, w, src, w0, w1, b1, ww, bw, out, st);
+  return PASNL_EUNSUPPORTED;
+}
+
+extern "C" int pasnl_sa_cell_pre(int b, int n, int c, int m, int k, int c1, int c2, const float* xyz, const float* feature,
+                                 const float* proj, const int* idx, const float* new_xyz, const float* w0, const float* w1,
+                                 const float* b1, const float* ww, const float* bw, float* out, float* skip_max,
+                                 pasnl_stream_t stream) {
+  PASNL_REQUIRE((long)b * m == 0 || new_xyz, PASNL_ENULL);
+  return sa_cell_pre_entry(b, n, c, m, k, c1, c2, xyz, feature, proj, idx, new_xyz, w0, w1, b1, ww, bw, out, skip_max, nullptr,
+                           nullptr, stream);
+}
+
+extern "C" int pasnl_sa_cell_pre_centre0(int b, int n, int c, int m, int k, int c1, int c2, const float* xyz,
+                                         const float* feature, const float* proj, const int* idx, const float* w0,
+                                         const float* w1, const float* b1, const float* ww, const float* bw, float* out,
+                                         float* skip_max, float* new_xyz, float* new_feature, pasnl_stream_t stream) {
+  PASNL_REQUIRE((long)b * m == 0 || (new_xyz && new_feature), PASNL_ENULL);
+  return sa_cell_pre_entry(b, n, c, m, k, c1, c2, xyz, feature, proj, idx, nullptr, w0, w1, b1, ww, bw, out, skip_max, new_xyz,
+                           new_feature, stream);
 }
 
 namespace pasnl {

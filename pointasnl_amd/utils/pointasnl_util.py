@@ -235,6 +235,50 @@ def sa_cell(xyz, feature, idx, new_xyz, mlp, is_training, bn_decay, weight_decay
     return view, skip
 
 
+SA_CELL_PREPROJECT = True  # layers that gather each point >= SA_PREPROJECT_REUSE times: conv0 once per point (pasnl_sa_project +
+#                            pasnl_sa_cell_pre); False = pasnl_sa_cell for every layer (A/B)
+SA_PREPROJECT_REUSE = 8    # npoint * nsample / N at or above which the table pays (cls layer2: 16)
+
+
+def sa_cell_pre_supported(b, n, c, npoint, nsample, mlp, feature):
+    """The layers sa_cell_pre takes: [c1, c1, out] with c1 in {32, 64, 128}, 16-byte feature rows, and enough reuse of every
+    source point (npoint * nsample / n).  (128-channel layers with few groups and 32 neighbours stay on the wide kernel.)"""
+    if not (SA_CELL_PREPROJECT and len(mlp) == 3 and mlp[0] == mlp[1] and mlp[0] in (32, 64, 128)):
+        return False
+    if c % 4 or c > 128 or nsample % 32 or npoint * nsample < SA_PREPROJECT_REUSE * n:
+        return False
+    if feature.is_contiguous() and feature.data_ptr() % 16:  # (a copy made by .contiguous() is aligned)
+        return False
+    return not (mlp[0] == 128 and nsample == 32 and b * npoint <= 2048)
+
+
+def sa_cell_pre(xyz, feature, idx, new_xyz, mlp, is_training, bn_decay, weight_decay, bn):
+    """sa_cell with conv0 split at its linear part: [xyz | feature] . W0[3:] + b0 once per source point (pasnl_sa_project), then
+    the cell adds (xyz - centre) . W0[0:3] to the gathered rows of that table (pasnl_sa_cell_pre / _centre0).  Same variables,
+    same outputs as sa_cell; `out` within fp32 rounding of it, `skip` bit-equal.  new_xyz = None: the centres are neighbour 0."""
+    b, n, c = feature.shape
+    _, p, k = idx.shape
+    xyz, feature, idx = xyz.contiguous(), feature.contiguous(), idx.contiguous()
+    w0, b0, w1, b1, ww, bw, ck = _sa_cell_weights(6 + c, mlp, bn, weight_decay)
+    proj = torch.empty((b, n, ck), dtype=torch.float32, device=xyz.device)
+    _hip.launch("pasnl_sa_project", "sa_project", b, n, c, ck, _hip.ptr(xyz), _hip.ptr(feature), _hip.ptr(w0), _hip.ptr(b0),
+                _hip.ptr(proj))
+    out = torch.empty((b, p, ck, 32), dtype=torch.float32, device=xyz.device)
+    skip = torch.empty((b, p, 6 + c), dtype=torch.float32, device=xyz.device)
+    if new_xyz is None:
+        cen = torch.empty((b, p, 3), dtype=torch.float32, device=xyz.device)
+        nf = torch.empty((b, p, 3 + c), dtype=torch.float32, device=xyz.device)
+        _hip.launch("pasnl_sa_cell_pre_centre0", "sa_cell_pre", b, n, c, p, k, ck, ck, _hip.ptr(xyz), _hip.ptr(feature),
+                    _hip.ptr(proj), _hip.ptr(idx), _hip.ptr(w0), _hip.ptr(w1), _hip.ptr(b1), _hip.ptr(ww), _hip.ptr(bw),
+                    _hip.ptr(out), _hip.ptr(skip), _hip.ptr(cen), _hip.ptr(nf))
+        return out, skip, cen, nf
+    new_xyz = new_xyz.contiguous()
+    _hip.launch("pasnl_sa_cell_pre", "sa_cell_pre", b, n, c, p, k, ck, ck, _hip.ptr(xyz), _hip.ptr(feature), _hip.ptr(proj),
+                _hip.ptr(idx), _hip.ptr(new_xyz), _hip.ptr(w0), _hip.ptr(w1), _hip.ptr(b1), _hip.ptr(ww), _hip.ptr(bw),
+                _hip.ptr(out), _hip.ptr(skip))
+    return out, skip
+
+
 def weight_net_hidden(xyz, hidden_units, scope, is_training, bn_decay=None, weight_decay=None, activation_fn="relu"):
     with tf_util.variable_scope(scope):
         net = xyz
@@ -755,12 +799,14 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         if fused and SA_CELL_GATHER:
             # grouping + skip max + local cell: one MFMA kernel reading the tables in place
             tf_util._require_inference(is_training)
+            # (the table pays where every source point is gathered many times; both centre forms take the same route)
+            cell = sa_cell_pre if sa_cell_pre_supported(batch_size, num_points, num_channel, npoint, nsample, mlp, feature) else sa_cell
             try:
                 if centre0:
-                    new_point, skip_spatial, new_xyz, new_feature = sa_cell(xyz, feature, idx, None, mlp, is_training,
-                                                                            bn_decay, weight_decay, bn)
+                    new_point, skip_spatial, new_xyz, new_feature = cell(xyz, feature, idx, None, mlp, is_training,
+                                                                         bn_decay, weight_decay, bn)
                 else:
-                    new_point, skip_spatial = sa_cell(xyz, feature, idx, new_xyz, mlp, is_training, bn_decay, weight_decay, bn)
+                    new_point, skip_spatial = cell(xyz, feature, idx, new_xyz, mlp, is_training, bn_decay, weight_decay, bn)
             except _hip.PasnlUnsupported:  # e.g. a row too wide for the LDS-resident weights: two-kernel / op-by-op path
                 new_point = None
         if centre0:
