@@ -532,6 +532,82 @@ int pasnl_knn_crop(int b, long n, long scan_stride, const float* points, const f
                    double radius, int* out_idx, double* out_d2, int* out_count, void* workspace, size_t workspace_bytes,
                    pasnl_stream_t stream);
 
+/* ---- The SemanticKITTI test loop on the device (SemanticKITTI/semantic_kitti_dataset_grid.py:192-245 `get_batch_gen('test')`
+ * and test_semantic_kitti_grid.py:128-180 `ModelTester.test`).  S scans live in ONE flat buffer: points (N,3) f32, scan i
+ * at rows [offsets[i], offsets[i+1]) (offsets (S+1) i64), its possibility at the same rows of a flat (N,) f64 buffer and
+ * its votes at the same rows of a flat (N,C) float16 buffer (row addresses are 64-bit).  One crop is picked, cropped,
+ * ordered and accounted by a chain of launches on one stream with no fork and no host synchronisation; the crop travels
+ * between them as a device descriptor: */
+typedef struct pasnl_scan_crop {
+  long long offset;   /* first row of the scan in the flat buffers                  */
+  int cloud;          /* cloud_ind (D:224)                                           */
+  int pick;           /* pick_idx inside the scan (D:225)                            */
+  int n;              /* the scan's point count                                      */
+  int k;              /* num_point + buffer of this crop (D:270)                     */
+  float cx, cy, cz;   /* the centre: points[offset + pick] (D:266)                   */
+  int pad;
+} pasnl_scan_crop_t;
+
+/* Pick (D:224-225): cloud = argmin(min_possibility[0..S)), then pick = argmin(possibility of that scan) -- the FIRST index
+ * among equal minima at both levels, numpy's NaN rule (the first NaN wins, -0 == +0).  k: ONE device int, this crop's
+ * num_point + buffer (drawn on the host).  -> desc (one descriptor), out_cloud (one int, NULL: not wanted).  One
+ * workgroup, a 64-bit (value, index) reduction. */
+int pasnl_scan_pick(int s, const long long* offsets, const double* possibility, const double* min_possibility,
+                    const float* points, const int* k, pasnl_scan_crop_t* desc, int* out_cloud, pasnl_stream_t stream);
+
+/* pasnl_knn_crop's k form for b crops whose scan, centre and k are the descriptors desc[0..b) on the device (the same
+ * kernels behind a template flag; results bit-identical to pasnl_knn_crop on the same scan, centre and k).  nmax: the
+ * largest scan's count (the grid is sized for it; blocks past a crop's own count exit); kcap >= every desc[c].k.
+ * workspace: pasnl_knn_crop_workspace_bytes(b, nmax) bytes. */
+int pasnl_knn_crop_indirect(int b, long nmax, const float* points, const pasnl_scan_crop_t* desc, int kcap, int* out_idx,
+                            double* out_d2, int* out_count, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
+/* The rest of crop_pc (D:271-277) for b crops: rank the desc[c].k selected entries (idx ascending, d2 f64: the output of
+ * pasnl_knn_crop_indirect, rows of kcap) by (d2, index) -- sklearn's nearest-first order, ties by the lowest index --
+ * then out_select[c][j] = nearest_first[perm[c][j]] for j < num_point (perm (b,num_point) i32: the first num_point
+ * entries of the host's rng.shuffle(arange(k)), D:287-291), and out_points[c][j] = points[offset + out_select[c][j]]
+ * (the batch's (b,num_point,3) model input).  One workgroup per crop sorts in LDS: kcap <= 14336, else
+ * PASNL_EUNSUPPORTED. */
+int pasnl_crop_order_permute(int b, const pasnl_scan_crop_t* desc, const float* points, const int* idx, const double* d2, int kcap,
+                             const int* perm, int num_point, int* out_select, float* out_points, pasnl_stream_t stream);
+
+/* The possibility update of one crop (D:231-234), in the reference's dtypes: dists = ((dx*dx)+dy*dy)+dz*dz in f32 with
+ * dx = (float)((double)x - (double)cx); delta = (1 - dists / max(dists))^2 in f32 (max propagates NaN);
+ * possibility[idx] = possibility[idx] + (double)delta with the LAST occurrence of a repeated index winning (numpy
+ * fancy-index +=); then min_possibility[cloud] = min(possibility of the scan) (NaN propagates).  select: (num_point) i32
+ * indices into the scan.  win: nmax device ints, all -1 before the call and after it (pasnl_scan_scratch_init).
+ * scratch: 4 device bytes.  Three launches. */
+int pasnl_scan_possibility_update(int num_point, const pasnl_scan_crop_t* desc, const float* points, const int* select,
+                                  double* possibility, double* min_possibility, int* win, float* scratch, pasnl_stream_t stream);
+
+/* win := -1 for n ints (the scratch of the update and the vote). */
+int pasnl_scan_scratch_init(long n, int* win, pasnl_stream_t stream);
+
+/* The votes of b crops (T:147-154), crop after crop in batch order: probs = softmax(values[c][j]) in f32 (is_logits;
+ * otherwise values are the probabilities), then for every class
+ * new = fp16( (float)fp16(smooth_old * old) + smooth_new * probs ): smooth_old the float16 bits of fp16(test_smooth),
+ * smooth_new = float32(1 - test_smooth); a repeated index within a crop: the last occurrence wins.  values (b,num_point,C)
+ * f32; select (b,num_point) i32; cloud (b) i32 device; offsets (S+1) i64; test_probs: the flat (N,C) float16 buffer.
+ * win: as in pasnl_scan_possibility_update.  Two launches per crop. */
+int pasnl_scan_vote(int b, int num_point, int c, const float* values, int is_logits, const int* select, const int* cloud,
+                    const long long* offsets, unsigned short smooth_old, float smooth_new, void* test_probs, int* win,
+                    pasnl_stream_t stream);
+
+/* proj_inds (D:168-169, 182-183: sklearn KDTree(sub).query(raw)): for each of n_raw raw points the nearest of n_sub
+ * sub-sampled points by the f64 key ((dx*dx)+(dy*dy))+(dz*dz) of the f32 coordinates, ties to the LOWEST index (sklearn:
+ * tree order).  A uniform grid of nx*ny*nz cells of edge h from (ox,oy,oz) (chosen by the caller; every sub point must lie
+ * inside it) is counting-sorted, then every raw point searches rings of cells outwards until no unexamined cell can hold a
+ * closer or tying point (a conservative margin of 1e-6 h).  workspace: pasnl_scan_reproject_workspace_bytes(n_sub, cells). */
+size_t pasnl_scan_reproject_workspace_bytes(long n_sub, long cells);
+int pasnl_scan_reproject(long n_sub, const float* sub, long n_raw, const float* raw, double ox, double oy, double oz, double h,
+                         int nx, int ny, int nz, int* out_proj, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
+/* Labels (T:165-180): pred = argmax over the float16 row probs[proj[j]] (C classes, the FIRST maximum; a NaN wins as in
+ * numpy), out[j] = ((pred >> 16) << 16) + lut[pred & 0xFFFF] as uint32.  proj (n_raw) i32 in [0, n_sub) (NULL: the
+ * identity); lut (nlut) i32 with nlut >= c. */
+int pasnl_scan_labels(long n_raw, const int* proj, const void* probs, int c, const int* lut, int nlut, unsigned* out,
+                      pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

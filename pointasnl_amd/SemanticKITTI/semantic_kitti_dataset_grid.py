@@ -8,7 +8,9 @@ with ONE exact selection (`pasnl_knn_crop`, csrc/crop.hip; no tree is built) -- 
 structure, the same SET of points (ranked by the float64 squared distance sklearn ranks by); a tie at the k-th distance
 goes to the lowest indices (and `query_radius` lists its points by ascending index, sklearn in its tree's order: crop_pc
 shuffles them at once).  `crop_pc` below is the reference's flow on top of it: shuffle, truncate, duplicate-pad with the
-caller's numpy RNG, on the host as there.  Datasets, the possibility bookkeeping and the tf.data plumbing are out of scope.
+caller's numpy RNG, on the host as there.  The test loop around it -- possibility init, pick, crop, possibility update,
+votes and reprojection (:192-245 and test_semantic_kitti_grid.py) -- runs on the device in scan_tester.ScanTester.
+Datasets and the tf.data plumbing are out of scope.
 """
 import ctypes
 

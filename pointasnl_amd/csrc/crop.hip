@@ -64,10 +64,18 @@ __device__ __forceinline__ unsigned long long cr_key(const float* __restrict__ p
   return (unsigned long long)__double_as_longlong(d2);
 }
 
+// IND (pasnl_knn_crop_indirect): crop c reads its scan's offset, point count, centre and k from desc[c] (written on the device
+// by pasnl_scan_pick); `n` is then the largest scan's count -- the stride of the key rows -- and blocks past the crop's own
+// count have nothing to do.  IND = false is the direct form, unchanged.
+__device__ __forceinline__ long cr_n(const pasnl_scan_crop_t* desc, int c, long n) { return desc ? (long)desc[c].n : n; }
+
 // start state from k (or the radius): grid = b
+template <bool IND>
 __global__ __launch_bounds__(CR_THREADS) void crop_init_kernel(long n, int kcap, const int* __restrict__ kdev, double r2,
-                                                               unsigned* __restrict__ hist, CrState* __restrict__ state) {
+                                                               unsigned* __restrict__ hist, CrState* __restrict__ state,
+                                                               const pasnl_scan_crop_t* __restrict__ desc) {
   const int c = blockIdx.x;
+  if constexpr (IND) n = cr_n(desc, c, n);
   unsigned* h = hist + (size_t)c * CR_PASSES * CR_BINS;
   for (int i = threadIdx.x; i < CR_PASSES * CR_BINS; i += CR_THREADS) h[i] = 0u;
   if (threadIdx.x == 0) {
@@ -76,7 +84,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_init_kernel(long n, int kcap,
     if (r2 >= 0.0) {  // radius form: key <= bits(r2)  <=>  key < bits(r2) + 1; nothing to select by rank
       s.prefix = (unsigned long long)__double_as_longlong(r2) + 1ull; s.shift = 0; s.r = 0; s.done = 1;
     } else {
-      long k = kdev ? (long)kdev[c] : (long)kcap;
+      long k = IND ? (long)desc[c].k : (kdev ? (long)kdev[c] : (long)kcap);
       k = k < (long)kcap ? k : (long)kcap;
       if (k <= 0) { s.prefix = 0ull; s.shift = 0; s.r = 0; s.done = 1; }
       else if (k >= n) { s.prefix = 1ull; s.shift = 63; s.r = 0; s.done = 1; }  // every key (bit 63 is clear, NaNs included)
@@ -134,10 +142,11 @@ __device__ __forceinline__ CrState cr_advance(int p, const CrState prev, const u
 }
 
 // pass P: grid = (nblk, b)
-template <int P>
+template <int P, bool IND>
 __global__ __launch_bounds__(CR_THREADS) void crop_pass_kernel(long n, long scan_stride, const float* __restrict__ points,
                                                                const float* __restrict__ centres, unsigned long long* __restrict__ keys,
-                                                               unsigned* __restrict__ hist, CrState* __restrict__ state) {
+                                                               unsigned* __restrict__ hist, CrState* __restrict__ state,
+                                                               const pasnl_scan_crop_t* __restrict__ desc) {
   __shared__ unsigned lh[CR_BINS];
   __shared__ int sh[CR_THREADS / 64 + 3];
   const int c = blockIdx.y, tid = threadIdx.x;
@@ -155,13 +164,18 @@ __global__ __launch_bounds__(CR_THREADS) void crop_pass_kernel(long n, long scan
   } else if (s.done) {
     // k <= 0, k >= n or the radius form: only the keys are needed
   }
+  unsigned long long* kc = keys + (size_t)c * n;
+  if constexpr (IND) {
+    n = cr_n(desc, c, n);
+    if ((long)blockIdx.x * CR_BLOCK >= n) return;  // (uniform) a block past this crop's scan
+  }
   for (int i = tid; i < CR_BINS; i += CR_THREADS) lh[i] = 0u;
   __syncthreads();
-  unsigned long long* kc = keys + (size_t)c * n;
   const long i0 = (long)blockIdx.x * CR_BLOCK + (long)tid * CR_ITEMS;
   if constexpr (P == 0) {
-    const float* pc = points + (size_t)c * scan_stride * 3;
-    const double cx = (double)centres[c * 3], cy = (double)centres[c * 3 + 1], cz = (double)centres[c * 3 + 2];
+    const float* pc = IND ? points + (size_t)desc[c].offset * 3 : points + (size_t)c * scan_stride * 3;
+    const float* cc = IND ? &desc[c].cx : centres + c * 3;
+    const double cx = (double)cc[0], cy = (double)cc[1], cz = (double)cc[2];
 #pragma unroll
     for (int e = 0; e < CR_ITEMS; ++e) {
       const long i = i0 + e;
@@ -196,9 +210,10 @@ __device__ __forceinline__ CrState cr_final(const CrState* __restrict__ st, cons
   return cr_advance(CR_PASSES, s, hist_c + (size_t)(CR_PASSES - 1) * CR_BINS, sh);
 }
 
+template <bool IND>
 __global__ __launch_bounds__(CR_THREADS) void crop_count_kernel(long n, const unsigned long long* __restrict__ keys,
                                                                 const unsigned* __restrict__ hist, CrState* __restrict__ state,
-                                                                int* __restrict__ blk) {
+                                                                int* __restrict__ blk, const pasnl_scan_crop_t* __restrict__ desc) {
   __shared__ int sh[CR_THREADS / 64 + 3];
   __shared__ int tot[2];
   const int c = blockIdx.y, tid = threadIdx.x;
@@ -208,6 +223,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_count_kernel(long n, const un
   if (tid < 2) tot[tid] = 0;
   __syncthreads();
   const unsigned long long* kc = keys + (size_t)c * n;
+  if constexpr (IND) n = cr_n(desc, c, n);
   const long i0 = (long)blockIdx.x * CR_BLOCK + (long)tid * CR_ITEMS;
   int below = 0, on = 0;
 #pragma unroll
@@ -226,10 +242,11 @@ __global__ __launch_bounds__(CR_THREADS) void crop_count_kernel(long n, const un
   if (tid < 2) blk[((size_t)c * gridDim.x + blockIdx.x) * 2 + tid] = tot[tid];
 }
 
+template <bool IND>
 __global__ __launch_bounds__(CR_THREADS) void crop_write_kernel(long n, int kcap, const unsigned long long* __restrict__ keys,
                                                                 const CrState* __restrict__ state, const int* __restrict__ blk,
                                                                 int* __restrict__ out_idx, double* __restrict__ out_d2,
-                                                                int* __restrict__ out_count) {
+                                                                int* __restrict__ out_count, const pasnl_scan_crop_t* __restrict__ desc) {
   __shared__ int shb[2][CR_THREADS / 64];
   __shared__ int base[2];
   const int c = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -251,6 +268,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_write_kernel(long n, int kcap
     }
   }
   const unsigned long long* kc = keys + (size_t)c * n;
+  if constexpr (IND) n = cr_n(desc, c, n);
   const long i0 = (long)blockIdx.x * CR_BLOCK + (long)tid * CR_ITEMS;
   unsigned long long key[CR_ITEMS];
   int below = 0, on = 0;
@@ -285,6 +303,21 @@ __global__ __launch_bounds__(CR_THREADS) void crop_write_kernel(long n, int kcap
   }
 }
 
+template <bool IND>
+static void cr_launch(int b, long n, long scan_stride, const float* points, const float* centres, const int* k, int kcap, double r2,
+                      int* out_idx, double* out_d2, int* out_count, const CrWs& w, const pasnl_scan_crop_t* desc, hipStream_t s) {
+  const long nblk = (n + CR_BLOCK - 1) / CR_BLOCK;
+  hipLaunchKernelGGL(crop_init_kernel<IND>, dim3(b), dim3(CR_THREADS), 0, s, n, kcap, k, r2, w.hist, w.state, desc);
+  const dim3 grid((unsigned)nblk, (unsigned)b);
+  hipLaunchKernelGGL((crop_pass_kernel<0, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<1, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<2, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<3, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<4, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL(crop_count_kernel<IND>, grid, dim3(CR_THREADS), 0, s, n, w.keys, w.hist, w.state, w.blk, desc);
+  hipLaunchKernelGGL(crop_write_kernel<IND>, grid, dim3(CR_THREADS), 0, s, n, kcap, w.keys, w.state, w.blk, out_idx, out_d2, out_count, desc);
+}
+
 }  // namespace pasnl
 
 using namespace pasnl;
@@ -301,19 +334,20 @@ extern "C" int pasnl_knn_crop(int b, long n, long scan_stride, const float* poin
   PASNL_REQUIRE(b > 0 && n > 0 && n < (1l << 31) && kcap > 0 && (scan_stride == 0 || scan_stride >= n), PASNL_EINVAL);
   PASNL_REQUIRE(!(radius != radius), PASNL_EINVAL);  // NaN radius
   PASNL_REQUIRE(points && centres && out_idx && out_count && workspace, PASNL_ENULL);
-  const long nblk = (n + CR_BLOCK - 1) / CR_BLOCK;
   CrWs w;
   PASNL_REQUIRE(workspace_bytes >= cr_layout(b, n, static_cast<char*>(workspace), &w), PASNL_EWORKSPACE);
   hipStream_t s = pasnl_hip_stream(stream);
   const double r2 = radius > 0.0 ? radius * radius : -1.0;  // sklearn: reduced radius r*r in double, inclusive
-  hipLaunchKernelGGL(crop_init_kernel, dim3(b), dim3(CR_THREADS), 0, s, n, kcap, k, r2, w.hist, w.state);
-  const dim3 grid((unsigned)nblk, (unsigned)b);
-  hipLaunchKernelGGL(crop_pass_kernel<0>, grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state);
-  hipLaunchKernelGGL(crop_pass_kernel<1>, grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state);
-  hipLaunchKernelGGL(crop_pass_kernel<2>, grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state);
-  hipLaunchKernelGGL(crop_pass_kernel<3>, grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state);
-  hipLaunchKernelGGL(crop_pass_kernel<4>, grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state);
-  hipLaunchKernelGGL(crop_count_kernel, grid, dim3(CR_THREADS), 0, s, n, w.keys, w.hist, w.state, w.blk);
-  hipLaunchKernelGGL(crop_write_kernel, grid, dim3(CR_THREADS), 0, s, n, kcap, w.keys, w.state, w.blk, out_idx, out_d2, out_count);
+  cr_launch<false>(b, n, scan_stride, points, centres, k, kcap, r2, out_idx, out_d2, out_count, w, nullptr, s);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_knn_crop_indirect(int b, long nmax, const float* points, const pasnl_scan_crop_t* desc, int kcap, int* out_idx,
+                                       double* out_d2, int* out_count, void* workspace, size_t workspace_bytes, pasnl_stream_t stream) {
+  PASNL_REQUIRE(b > 0 && nmax > 0 && nmax < (1l << 31) && kcap > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(points && desc && out_idx && out_count && workspace, PASNL_ENULL);
+  CrWs w;
+  PASNL_REQUIRE(workspace_bytes >= cr_layout(b, nmax, static_cast<char*>(workspace), &w), PASNL_EWORKSPACE);
+  cr_launch<true>(b, nmax, 0, points, nullptr, nullptr, kcap, -1.0, out_idx, out_d2, out_count, w, desc, pasnl_hip_stream(stream));
   return pasnl_launch_status();
 }
