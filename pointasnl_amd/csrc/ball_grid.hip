@@ -54,23 +54,6 @@ constexpr int BG_U = 4;                        // tier 2: candidates per lane an
 constexpr float BG_DENSE_HITS = 12.f;          // expected hits per query above which a workgroup starts in tier 2
 static_assert(BG_REGION == 4096 && BG_REGION >= BG_STAGE_ROWS * 128, "a wave region stages 32 rows of 128 bytes and holds 4 KiB of bit rows");
 
-#ifdef PASNL_TUNING
-// phase probe (tuning build only; tools/ballprobe.py): cycles of wave 0 of workgroup (0, gridDim.y / 2), summed over its rounds
-// [0] build  [1] -  [2] round set-up + run table  [3] walk  [4] sorting network + rows out  [5] tier 2 / round end
-// [6] tier-2 passes  [7] steps
-__device__ unsigned long long bg_probe[8];
-#define BG_MARK(i)                                                                         \
-  do {                                                                                     \
-    if (probe) { const long long t_ = clock64(); atomicAdd(&bg_probe[i], (unsigned long long)(t_ - tmark)); tmark = clock64(); } \
-  } while (0)
-#define BG_COUNT(i, v) do { if (probe) atomicAdd(&bg_probe[i], (unsigned long long)(v)); } while (0)
-// workgroup timeline (tools/ballprobe.py --timeline): {start, end, HW_ID, XCC_ID} of the first 8192 workgroups of a launch
-__device__ unsigned long long bg_trace[8192 * 4];
-#else
-#define BG_MARK(i) do { } while (0)
-#define BG_COUNT(i, v) do { } while (0)
-#endif
-
 __device__ __forceinline__ float bg_dist2(float qx, float qy, float qz, const float4 v) {
   // ((dx*dx)+(dy*dy))+(dz*dz) with x and y on one packed instruction each (identical IEEE operations per component)
   const pasnl_f32x2 d = pasnl_f32x2{v.x, v.y} - pasnl_f32x2{qx, qy};
@@ -154,16 +137,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bi = blockIdx.y;
   const float* cloud = xyz1 + (size_t)bi * n * 3;
-#ifdef PASNL_TUNING
-  const bool probe = tid == 0 && blockIdx.x == 0 && blockIdx.y == gridDim.y / 2;
-  long long tmark = clock64();
-  const int wgid = blockIdx.y * gridDim.x + blockIdx.x;
-  if (tid == 0 && wgid < 8192) {
-    bg_trace[wgid * 4] = __builtin_amdgcn_s_memrealtime();
-    bg_trace[wgid * 4 + 2] = __builtin_amdgcn_s_getreg((4 /*HW_ID*/) | (0 << 6) | (31 << 11));
-    bg_trace[wgid * 4 + 3] = __builtin_amdgcn_s_getreg((20 /*XCC_ID*/) | (0 << 6) | (31 << 11));
-  }
-#endif
 
   // the thread's query, requested before anything else: it arrives during the build (under load a global load takes
   // microseconds, and the round would start by waiting for it)
@@ -294,7 +267,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
     const int k = i * BG_THREADS + tid;
     if (k < n) spt[(int)cstart[pcell[i]] + prank[i]] = make_float4(px[i], py[i], pz[i], __int_as_float(k));
   }
-  BG_MARK(0);
 
 
   // The nine runs of x-adjacent cells around a query.
@@ -409,7 +381,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
 #pragma unroll
         for (int t = 0; t < 9; ++t) tab[t * 64] = 0;
       }
-      BG_MARK(2);
       // (3) the flat walk: two candidates per step, software-pipelined: the records of the NEXT pair are requested before the
       // current pair is evaluated (a wave alone on its SIMD otherwise waits out one LDS round trip per step), and the
       // table entry one step earlier still.  The walk's state is ONE register in the table's own format,
@@ -453,7 +424,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
         c += (l1 && dd[1] < thr2) ? 1 : 0;                                                                              \
         c = min(c, BG_CAP); /* a count that reaches BG_CAP stays there: the lane's row then comes from tier 2 */        \
         m0 = __builtin_amdgcn_ballot_w64(cur >= ONE); /* lanes with a pair to examine in the NEXT step: the exit test */ \
-        BG_COUNT(7, 1);                                                                                                 \
       }
       advance(true, 0u);
       BgPair ra, rb;
@@ -466,7 +436,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
         PASNL_BG_STEP(rb, ra)
       }
 #undef PASNL_BG_STEP
-      BG_MARK(3);
       const bool done = live && !longrun && c < BG_CAP;  // the lane's list is complete and exact
       need2 = live && !done;
       const unsigned long long donemask = __builtin_amdgcn_ballot_w64(done);
@@ -564,7 +533,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
           }
         }
         if (done) pts_cnt[(size_t)bi * m + j] = min(c, nsample);
-        BG_MARK(4);
       }
     }
 
@@ -635,7 +603,6 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
       for (int pass = 0; pass < 64 / LP; ++pass) {
         const bool act = need2 && (lane / LP) == pass;
         if (!__any(act)) continue;
-        BG_COUNT(6, 1);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         {
@@ -684,11 +651,7 @@ __global__ __launch_bounds__(BG_THREADS, NW32 <= 32 ? 6 : 4) void ball_grid_kern
         }
       }
     }
-    BG_MARK(5);
   }
-#ifdef PASNL_TUNING
-  if (tid == 0 && wgid < 8192) bg_trace[wgid * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // Host side.  Returns PASNL_OK / PASNL_ELAUNCH, or PASNL_EUNSUPPORTED when the shape is not covered (the caller then
@@ -731,19 +694,3 @@ int ball_grid_launch(int b, int n, int m, float radius, float thr2, int nsample,
 
 }  // namespace pasnl
 
-#ifdef PASNL_TUNING
-extern "C" int pasnl_ball_trace_read(unsigned long long* host, int count) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(pasnl::bg_trace), sizeof(unsigned long long) * 4 * count) == hipSuccess ? 0 : -1;
-}
-extern "C" int pasnl_ball_occupancy(int n) {  // workgroups per CU the runtime computes for the n <= 1024 instantiation
-  int nb = -1;
-  const size_t lds = (size_t)n * 16 + pasnl::BG_WAVES * pasnl::BG_REGION + (size_t)((pasnl::BG_NC + 3 + 1) & ~1) * 2;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pasnl::ball_grid_kernel<32>, pasnl::BG_THREADS, lds) != hipSuccess) return -1;
-  return nb;
-}
-extern "C" int pasnl_ball_probe_read(unsigned long long* host8) {
-  if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(pasnl::bg_probe), sizeof(pasnl::bg_probe)) != hipSuccess) return -1;
-  unsigned long long zero[8] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(pasnl::bg_probe), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -52,43 +52,6 @@ __device__ __forceinline__ int kappa(int t, int h) { return (t & 3) + 8 * (t >> 
 //   V[kappa(t,h)][c0 + (l&31)] is a conflict-free LDS row read.
 //   K rows are stored with stride CB+1 so that the A-operand read K[l&31][2t+h] is conflict-free.
 // =============================================================================================
-// Diagnostic builds only (make probe: -DPASNL_SA_CELL_PROBE=<level> [-DPASNL_SA_ABLATE=<mask>] -> libpasnl_hip_probe*.so,
-// tools/sa_cell_probe.py): s_memtime marks at the phase boundaries of a tile, summed over all waves into sa_probe[].
-// Level 2 adds marks around explicit vmcnt(0) waits (tile start, every chunk), which separates "waiting for gathered
-// rows" from matrix work at the price of perturbing the LDS prefetch.  The ablation mask removes one ingredient at a
-// time (results are then wrong; only the time matters): 1 skip maxima, 2 global operand loads, 4 output stores.
-#ifdef PASNL_SA_CELL_PROBE
-__device__ unsigned long long sa_probe[16];
-__device__ unsigned long long nl_probe[16];
-#define SA_MARK0(t) do { __builtin_amdgcn_sched_barrier(0); t = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#if PASNL_SA_CELL_PROBE >= 1
-#define SA_MARK(t) SA_MARK0(t)
-#else
-#define SA_MARK(t) t = 0   /* level 0: only the wave's total (two marks per wave: the code is the production code) */
-#endif
-#define SA_PROBE(...) __VA_ARGS__
-#if PASNL_SA_CELL_PROBE >= 2
-#define SA_MARK2(t) SA_MARK(t)
-#define SA_WAIT_VM() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define SA_MARK2(t) t = 0
-#define SA_WAIT_VM()
-#endif
-#else
-#define SA_MARK(t)
-#define SA_MARK2(t)
-#define SA_WAIT_VM()
-#define SA_PROBE(...)
-#endif
-// streaming (non-temporal) stores of the cell's (C2 x 32)-per-group output: written once, read by the next kernel from HBM
-// anyway, and without the hint 67-268 MB per launch wash through every XCD's L2 (cls step 1.497 -> 1.483 ms; the cell itself
-// takes the same time)
-#ifndef PASNL_SA_NT
-#define PASNL_SA_NT 1
-#endif
-#ifndef PASNL_SA_ABLATE
-#define PASNL_SA_ABLATE 0
-#endif
 
 constexpr int NL_KB = 32;  // keys per block
 
@@ -131,7 +94,6 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_attention_mfma_kernel(int p, in
 #pragma unroll
     for (int r = 0; r < 16; ++r) O[c][r] = 0.f;
   float mrun = -INFINITY, lrun = 0.f;
-  SA_PROBE(unsigned long long n0, n1, n2, n3, n4, nk0, a_st = 0, a_s = 0, a_sm = 0, a_pv = 0, a_blk = 0; SA_MARK0(nk0);)
 
   // Register prefetch (cb <= 64): the [K | V] rows of block i+1 are requested before the products of block i and written
   // to the wave's LDS region after them, so a wave overlaps ITS OWN memory round trip with its own matrix work.  (More
@@ -153,7 +115,6 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_attention_mfma_kernel(int p, in
   }
 
   for (int base = wave * NL_KB; base < n; base += SPLIT * NL_KB) {
-    SA_MARK(n0);
     const int cnt = min(NL_KB, n - base);
     if constexpr (PF) {
       // rows past cnt are zero-filled: their probabilities are 0, and 0 * stale-LDS-NaN must not reach the accumulator
@@ -191,7 +152,6 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_attention_mfma_kernel(int p, in
     }
     }
     // (LDS operations of one wave execute in order: no barrier needed before reading the region back)
-    SA_MARK(n1);
     // ---- S^T = K_blk . Q^T
     f32x16 S;
 #pragma unroll
@@ -206,7 +166,6 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_attention_mfma_kernel(int p, in
 #pragma unroll
       for (int t = 0; t < 16; ++t) vop[t] = vcol0[kappa(t, h) * CB];
     }
-    SA_MARK(n2);
     // ---- online softmax over this lane's 16 keys (+ the other half-wave's 16)
     float tmax = -INFINITY;
     if (cnt < NL_KB) {  // keys to mask exist only in the last block of a cloud whose size is not a multiple of 32
@@ -227,7 +186,6 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_attention_mfma_kernel(int p, in
     psum += __shfl_xor(psum, 32);
     lrun = lrun * alpha + psum;
     mrun = mnew;
-    SA_MARK(n3);
     // ---- O^T = alpha * O^T + V^T . P^T
 #pragma unroll
     for (int c = 0; c < CB / 32; ++c) {
@@ -238,17 +196,7 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_attention_mfma_kernel(int p, in
       for (int t = 0; t < 16; ++t)
         O[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(c == 0 ? vop[t] : vcol[kappa(t, h) * CB], S[t], O[c], 0, 0, 0);
     }
-    SA_MARK(n4);
-    SA_PROBE(a_st += n1 - n0; a_s += n2 - n1; a_sm += n3 - n2; a_pv += n4 - n3; a_blk += 1;)
   }
-#ifdef PASNL_SA_CELL_PROBE
-  SA_MARK0(n4);
-  if (lane == 0) {
-    atomicAdd(&nl_probe[0], a_st); atomicAdd(&nl_probe[1], a_s); atomicAdd(&nl_probe[2], a_sm); atomicAdd(&nl_probe[3], a_pv);
-    atomicAdd(&nl_probe[4], a_blk); atomicAdd(&nl_probe[5], n4 - nk0); atomicAdd(&nl_probe[6], 1ull);
-  }
-  SA_MARK0(nk0);
-#endif
 
   if constexpr (SPLIT > 1) {
     // ---- merge the SPLIT partial results: wave w > 0 parks (m, l, O) in its own LDS region, wave 0 folds them in
@@ -579,9 +527,7 @@ __global__ __launch_bounds__(SPLIT * 64, 2) void nl_attention_pair_kernel(int p,
       softmax_piece(S0, 0, alpha0, t);
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifndef PASNL_NL_PAIR_NOLOAD  // (timing ablation: the loop without its refills)
     load_k();
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // ---- O0 += V . P0 with softmax(S1) in its shadow
 #pragma unroll
@@ -594,9 +540,7 @@ __global__ __launch_bounds__(SPLIT * 64, 2) void nl_attention_pair_kernel(int p,
 #pragma unroll
     for (int t = 0; t < 16; ++t) O[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vreg[t], S1[t], O[1], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
-#ifndef PASNL_NL_PAIR_NOLOAD
     load_v();
-#endif
     __builtin_amdgcn_sched_barrier(0);
   }
 
@@ -1020,16 +964,13 @@ __global__ __launch_bounds__(256) void sa_local_cell_kernel(long groups, int k, 
     }
     // M[c2 = cb*32 + kappa(r,h)][j = ql] -> out[g][c2*32 + j]
     float* o = out + (size_t)g * C2 * 32;
+    // streaming (non-temporal) stores of the cell's (C2 x 32)-per-group output: written once, read by the next kernel from HBM
+    // anyway, and without the hint 67-268 MB per launch wash through every XCD's L2 (cls step 1.497 -> 1.483 ms; the cell itself
+    // takes the same time)
 #pragma unroll
     for (int cb = 0; cb < C2 / 32; ++cb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-#if PASNL_SA_NT
-        __builtin_nontemporal_store(M[cb][r], &o[(size_t)(cb * 32 + kappa(r, h)) * 32 + ql]);
-#else
-        o[(size_t)(cb * 32 + kappa(r, h)) * 32 + ql] = M[cb][r];
-#endif
-      }
+      for (int r = 0; r < 16; ++r) __builtin_nontemporal_store(M[cb][r], &o[(size_t)(cb * 32 + kappa(r, h)) * 32 + ql]);
   }
 }
 
@@ -1089,7 +1030,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
                                                          float* __restrict__ out) {
   static_assert(!PRE || (VEC && !XYZ3 && !SINGLE), "the pre-projected form takes 16-byte rows and two convolutions");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  SA_PROBE(unsigned long long pentry; SA_MARK0(pentry);)
   const int cf = w - 6;
   const int wi = 8 + cf;                            // internal width
   const int wp = (wi + 31) & ~31;
@@ -1186,9 +1126,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
   const int step = xcd_map ? (int)(gridDim.x >> 3) * NW : (int)gridDim.x * NW;
   const int step_q = step / m, step_r = step - step_q * m;
   int cl = first / m, pj = first - cl * m;  // position in this workgroup's list: cloud slot, point
-  SA_PROBE(unsigned long long pk0, pg0, pt0, pt1, pt2, pt3, pc0, pc1;
-           unsigned long long a_pro = 0, a_start = 0, a_conv0 = 0, a_cwait = 0, a_conv1 = 0, a_epi = 0, a_tiles = 0;)
-  SA_PROBE(SA_MARK0(pk0);)
   // Operands of one chunk for this lane.  Every load is unconditional with a clamped address (a conditional load
   // compiles to its own exec-masked basic block); columns outside the feature row exist only in the LAST chunk of
   // a row that is not a multiple of 32 wide (and in chunk 0's first 8 columns, which are overwritten below), so
@@ -1204,11 +1141,7 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
   float xs[16];                          // PRE: a chunk of the current tile's rows, for the skip maxima only
   // operands [u0, u1) of chunk ch (VEC: whole 16-byte groups); the loops unroll, u0 / u1 are constants at every call
   auto load_part = [&](int ch, int u0, int u1) {
-    if constexpr ((PASNL_SA_ABLATE & 2) != 0) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t)
-        if (t >= u0 && t < u1) xr[t] = (float)(ch + t) * px;
-    } else if constexpr (VEC) {
+    if constexpr (VEC) {
       const int g0 = ch * 8 + 4 * h - 2;  // first 16-byte group of this lane's 16 columns (-2 in chunk 0)
 #pragma unroll
       for (int q = 0; q < 4; ++q)
@@ -1289,7 +1222,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
     cxn = src.new_xyz[g0 * 3]; cyn = src.new_xyz[g0 * 3 + 1]; czn = src.new_xyz[g0 * 3 + 2];
   }
   for (int li = first; li < my_groups; li += step) {
-    SA_MARK(pg0);
     const long bi = xcd_map ? xcd + 8 * cl : cl;
     const long g = bi * m + pj;
     pj += step_r;
@@ -1321,13 +1253,8 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
 #pragma unroll
         for (int cb = 0; cb < C2 / 32; ++cb) asm volatile("" : "+a"(M[cb]));  // M lives in AccVGPRs: no VALU ever reads it
       }
-      SA_MARK(pt0);
-      SA_PROBE(if (tile == 0) a_pro += pt0 - pg0;)
       // (this tile's rows were requested during the previous tile; now the indices of the following tile)
       inext = src.idx[(tile + 32 < ktile ? (size_t)g * k + tile + 32 : (size_t)g_next * k) + ql];
-      SA_WAIT_VM();
-      SA_MARK(pt1);
-      SA_PROBE(a_start += pt1 - pt0;)
 
       f32x16 H1T[C1 / 32];
       if constexpr (!PRE) {  // (PRE: the first conv0 step writes H1T from the gathered table rows)
@@ -1417,11 +1344,7 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         typedef __attribute__((address_space(3))) float lds_float;
         lds_float* srow = (lds_float*)(skl + ch * 32);
         asm volatile("" : "+v"(srow));
-#ifdef PASNL_SA_BT
-        constexpr int BT = PASNL_SA_BT;
-#else
         constexpr int BT = XYZ3 ? 2 : (C1 >= 128 ? 1 : 128 / C1);  // MFMA steps per batch (XYZ3: 6 steps = 3 batches of 2)
-#endif
         constexpr int NB = NS / BT;
         const float* wbase = VEC ? W0s + (size_t)(ch * 32 + 16 * h) * C1 + ql : W0s + (size_t)(ch * 32 + h) * C1 + ql;
         float wa[2][BT][C1 / 32];
@@ -1439,17 +1362,15 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
                 wa[(j + 1) & 1][u][ob] = wbase[(size_t)(RS * ((j + 1) * BT + u)) * C1 + ob * 32];
           }
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (!(PASNL_SA_ABLATE & 1)) {
-            // the skip maxima of THIS batch's operands, next to the MFMAs that consume the same registers: folded in one go at
-            // the top of the chunk they made the wave wait for the operand refills the previous chunk had only just requested
-            // (3.4 k of a 49.7-k-cycle tile: what the "no skip maxima" ablation gains); here they wait for what the MFMAs wait for
+          // the skip maxima of THIS batch's operands, next to the MFMAs that consume the same registers: folded in one go at
+          // the top of the chunk they made the wave wait for the operand refills the previous chunk had only just requested
+          // (3.4 k of a 49.7-k-cycle tile: what the "no skip maxima" ablation gains); here they wait for what the MFMAs wait for
 #pragma unroll
-            for (int u = 0; u < BT; ++u) {
-              const int t = j * BT + u;
-              // XYZ3: steps 3 (the constant-1 / zero columns) and 6, 7 (padding) hold no column the skip connection reads
-              if (XYZ3 && (t == 3 || t >= 6)) continue;
-              __hip_atomic_fetch_max(srow + RS * t, xr[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            }
+          for (int u = 0; u < BT; ++u) {
+            const int t = j * BT + u;
+            // XYZ3: steps 3 (the constant-1 / zero columns) and 6, 7 (padding) hold no column the skip connection reads
+            if (XYZ3 && (t == 3 || t >= 6)) continue;
+            __hip_atomic_fetch_max(srow + RS * t, xr[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
           }
 #pragma unroll
           for (int u = 0; u < BT; ++u)
@@ -1476,10 +1397,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       // ---- full chunks: one code path, so that the accumulators stay where they are across iterations
       for (int ch = 0; ch < nfull; ++ch) {
         chunk_steps(ch, std::integral_constant<int, 16>{}, std::true_type{});  // (the last refill of a tile is a dummy)
-        SA_MARK2(pc0);
-        SA_WAIT_VM();
-        SA_MARK2(pc1);
-        SA_PROBE(a_cwait += pc1 - pc0;)
       }
       // ---- the last chunk of a row whose width is not a multiple of 32: 8 or 16 steps (rows of W0 past the width and
       // the masked operands are zero, so steps past the last live column add nothing)
@@ -1505,8 +1422,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       // rows of the following tile (same group, or the first tile of the next one): they arrive during conv1.  (PRE: after
       // conv1's first block -- conv0's two steps would not cover the wait for the indices requested at the top of the tile)
       if constexpr (!PRE) request_rows(tile + 32 < ktile ? bi : bi_next, inext);
-      SA_MARK(pt2);
-      SA_PROBE(a_conv0 += pt2 - pt1;)
       // ReLU (the bias came with the MFMA); G: bias + ReLU
 #pragma unroll
       for (int ob = 0; ob < C1 / 32; ++ob)
@@ -1580,23 +1495,13 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         if (lane < cf) nfo[3 + lane] = nf0;
         if (lane + 64 < cf) nfo[3 + lane + 64] = nf1;
       }
-      SA_MARK(pt3);
-      SA_PROBE(a_conv1 += pt3 - pt2; a_tiles += 1;)
     }
     // M[c2 = cb*32 + kappa(r,h)][j = ql] -> out[g][c2*32 + j]
     float* o = out + (size_t)g * C2 * 32;
-    if ((PASNL_SA_ABLATE & 4) && cx == 12345.f) o = nullptr;  // ablation: keep M alive, store (almost) never
-    if (!(PASNL_SA_ABLATE & 4) || o == nullptr)
 #pragma unroll
     for (int cb = 0; cb < C2 / 32; ++cb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-#if PASNL_SA_NT
-        __builtin_nontemporal_store(M[cb][r], &o[(size_t)(cb * 32 + kappa(r, h)) * 32 + ql]);
-#else
-        o[(size_t)(cb * 32 + kappa(r, h)) * 32 + ql] = M[cb][r];
-#endif
-      }
+      for (int r = 0; r < 16; ++r) __builtin_nontemporal_store(M[cb][r], &o[(size_t)(cb * 32 + kappa(r, h)) * 32 + ql]);
     // the wave's LDS operations execute in order; the fences only keep the compiler from moving the reads up
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1614,38 +1519,10 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       }
     }
     __builtin_amdgcn_wave_barrier();
-    SA_MARK(pt0);
-    SA_PROBE(a_epi += pt0 - pt3;)
   }
-#ifdef PASNL_SA_CELL_PROBE
-  SA_MARK0(pt0);
-  if (lane == 0) {
-    atomicAdd(&sa_probe[0], a_pro); atomicAdd(&sa_probe[1], a_start); atomicAdd(&sa_probe[2], a_conv0);
-    atomicAdd(&sa_probe[3], a_cwait); atomicAdd(&sa_probe[4], a_conv1); atomicAdd(&sa_probe[5], a_epi);
-    atomicAdd(&sa_probe[6], a_tiles); atomicAdd(&sa_probe[7], pt0 - pk0); atomicAdd(&sa_probe[8], 1ull);
-    atomicAdd(&sa_probe[9], pk0 - pentry);
-  }
-#endif
 }
 
 #undef frow
-#ifdef PASNL_SA_CELL_PROBE
-}  // namespace pasnl
-// [prologue, start wait, conv0 (incl. chunk wait), chunk wait, conv1 + matmul, epilogue, tiles, wave total, waves,
-// weight staging] cycles
-// [staging, S = K.Q^T, softmax, O += V^T.P^T, blocks, wave loop total, waves] cycles
-extern "C" int pasnl_nl_probe_read(unsigned long long* host16) {
-  if (hipMemcpyFromSymbol(host16, HIP_SYMBOL(pasnl::nl_probe), sizeof(pasnl::nl_probe)) != hipSuccess) return -1;
-  unsigned long long zero[16] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(pasnl::nl_probe), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-extern "C" int pasnl_sa_cell_probe_read(unsigned long long* host16) {
-  if (hipMemcpyFromSymbol(host16, HIP_SYMBOL(pasnl::sa_probe), sizeof(pasnl::sa_probe)) != hipSuccess) return -1;
-  unsigned long long zero[16] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(pasnl::sa_probe), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-namespace pasnl {
-#endif
 
 
 // =============================================================================================
@@ -1822,28 +1699,23 @@ static int nl_pair_launch(int b, int p, int n, float qscale, const float* q, con
 }
 
 // Keys over workgroups (nl_attention_pair_kernel<., true>): for cb = 32 shapes whose b * ceil(p / 64) workgroups leave CUs empty
-// and whose key loops are long (n >= 4096).  -> kparts (1: not used) and the waves per workgroup.  Measured on the shapes of the
-// models (tools/nl_parts_sweep.py): four waves per workgroup; the number of parts that deals the workgroups evenly to the 256
+// and whose key loops are long (n >= 4096).  -> kparts (1: not used).  Measured on the shapes of the
+// models (tools/nl_parts_sweep.py): four waves per workgroup (NL_PARTS_SPLIT); the number of parts that deals the workgroups evenly to the 256
 // CUs -- the smallest k that minimises ceil(pairs k / 256) / k -- with >= 4 key blocks per wave: [8,1280,10240] 198 -> 128 us
 // at k = 8 (1280 workgroups = 5 per CU), [4,1024,8192] 90 -> 49 us at k = 4; key sets of 40 blocks ([8,320,1280], 18 us) gain
 // nothing and keep the plain form.
-struct NlParts { int kparts, split; };
-static NlParts nl_parts(int b, int p, int n, int cb) {
-  NlParts r{1, 1};
-  if (cb != 32 || n % NL_KB != 0) return r;
+constexpr int NL_PARTS_SPLIT = 4;
+static int nl_parts(int b, int p, int n, int cb) {
+  int kparts = 1;
+  if (cb != 32 || n % NL_KB != 0) return kparts;
   const long pairs = (long)b * ((p + 63) / 64), blocks = n / NL_KB;
-  if (pairs >= 224 || pairs <= 0 || blocks < 128) return r;  // (the plain form has a workgroup for ~every CU / short key loops)
-  const int split = 4;
+  if (pairs >= 224 || pairs <= 0 || blocks < 128) return kparts;  // (the plain form has a workgroup for ~every CU / short key loops)
   double best = 1.0;  // the plain form: one round of whole pairs
-  for (int k = 2; k <= 32 && (long)k * split * 4 <= blocks; ++k) {
+  for (int k = 2; k <= 32 && (long)k * NL_PARTS_SPLIT * 4 <= blocks; ++k) {
     const double t = (double)((pairs * k + 255) / 256) / (double)k;
-    if (t < best - 1e-9) { best = t; r.kparts = k; r.split = split; }
+    if (t < best - 1e-9) { best = t; kparts = k; }
   }
-  if (const char* e = tune_env("PASNL_NL_PARTS")) {  // tuning build only: "kparts,split"
-    int k = 1, sp = 8;
-    if (sscanf(e, "%d,%d", &k, &sp) == 2 && k >= 1 && (long)k * sp <= blocks) { r.kparts = k; r.split = sp; }
-  }
-  return r;
+  return kparts;
 }
 static size_t nl_parts_bytes(int b, int p, int kparts) {
   return (size_t)b * ((p + 63) / 64) * kparts * 2 * (32 / 2 + 2) * 64 * sizeof(float);
@@ -1871,14 +1743,9 @@ static int nl_mfma_dispatch(int b, int p, int n, float qscale, const float* q, c
     // KITTI layer 1_1: 160 -- 222 -> 200 us although 96 CUs stay empty) and no ragged key block
     const long pairs = (long)b * ((p + 63) / 64);
     const long blocks = (n + NL_KB - 1) / NL_KB;
-    const char* one = tune_env("PASNL_NL_PAIR");  // tuning only: "0" = never
-    const char* pm = tune_env("PASNL_NL_PAIR_MIN");  // tuning only
-    const long pair_min = pm && *pm ? atol(pm) : 128;
-    if (!staged && pairs >= pair_min && n % NL_KB == 0 && !(one && *one == '0')) {
+    if (!staged && pairs >= 128 && n % NL_KB == 0) {
       int want = 1;
       while (want < 8 && pairs * want < 2048 && want * 2 * 4 <= blocks) want *= 2;
-      const char* force = tune_env("PASNL_NL_SPLIT");
-      if (force && *force) want = atoi(force);
       if (want >= 8) return nl_pair_launch<8>(b, p, n, qscale, q, kv, out, st);
       if (want >= 4) return nl_pair_launch<4>(b, p, n, qscale, q, kv, out, st);
       if (want >= 2) return nl_pair_launch<2>(b, p, n, qscale, q, kv, out, st);
@@ -1893,8 +1760,6 @@ static int nl_mfma_dispatch(int b, int p, int n, float qscale, const float* q, c
   long blocks = (n + NL_KB - 1) / NL_KB;
   int want = 1;
   while (want < 8 && tiles * want < 4096 && want * 2 * 4 <= blocks) want *= 2;
-  const char* force = tune_env("PASNL_NL_SPLIT");  // tuning only
-  if (force && *force) want = atoi(force);
   if (CB == 128 && want > 4) want = 4;
   if constexpr (CB < 128) {  // (cb = 128: 4 wave regions fill the LDS; the 8-wave form would also spill)
     if (want >= 8) return nl_mfma_launch<CB, 8>(b, p, n, qscale, q, kv, out, staged, st);
@@ -1918,8 +1783,8 @@ extern "C" int pasnl_nl_attention(int b, int p, int n, int cb, const float* q, c
 }
 extern "C" size_t pasnl_nl_attention_workspace_bytes(int b, int p, int n, int cb) {
   if (b <= 0 || p <= 0 || n <= 0) return 0;
-  const NlParts np = nl_parts(b, p, n, cb);
-  return np.kparts > 1 ? nl_parts_bytes(b, p, np.kparts) : 0;
+  const int kparts = nl_parts(b, p, n, cb);
+  return kparts > 1 ? nl_parts_bytes(b, p, kparts) : 0;
 }
 extern "C" int pasnl_nl_attention_ws(int b, int p, int n, int cb, const float* q, const float* kv, float* out, int variant,
                                      void* workspace, size_t workspace_bytes, pasnl_stream_t stream) {
@@ -1943,15 +1808,12 @@ static int nl_attention_entry(int b, int p, int n, int cb, const float* q, const
     return PASNL_EUNSUPPORTED;  // cb=128 does not fit the one-query-per-lane register budget
   }
   if (cb == 32 && variant == 0 && workspace != nullptr) {  // keys over workgroups where the plain form leaves CUs empty
-    const NlParts np = nl_parts(b, p, n, cb);
-    if (np.kparts > 1) {
-      PASNL_REQUIRE(workspace_bytes >= nl_parts_bytes(b, p, np.kparts), PASNL_EWORKSPACE);
+    const int kparts = nl_parts(b, p, n, cb);
+    if (kparts > 1) {
+      PASNL_REQUIRE(workspace_bytes >= nl_parts_bytes(b, p, kparts), PASNL_EWORKSPACE);
       PASNL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, PASNL_EUNSUPPORTED);
       float* part = static_cast<float*>(workspace);
-      if (np.split >= 8) return nl_pair_parts_launch<8>(b, p, n, qscale, q, kv, out, np.kparts, part, st);
-      if (np.split >= 4) return nl_pair_parts_launch<4>(b, p, n, qscale, q, kv, out, np.kparts, part, st);
-      if (np.split >= 2) return nl_pair_parts_launch<2>(b, p, n, qscale, q, kv, out, np.kparts, part, st);
-      return nl_pair_parts_launch<1>(b, p, n, qscale, q, kv, out, np.kparts, part, st);
+      return nl_pair_parts_launch<NL_PARTS_SPLIT>(b, p, n, qscale, q, kv, out, kparts, part, st);
     }
   }
   if (cb == 32) return nl_mfma_dispatch<32>(b, p, n, qscale, q, kv, out, variant == 3, st);
@@ -2429,8 +2291,7 @@ extern "C" int pasnl_as_cell_wide_ld(int g, int as, int cb, int w, int ch, const
   PASNL_REQUIRE(lds <= 64 * 1024, PASNL_EUNSUPPORTED);
   const float qscale = LOG2E / sqrtf((float)cb);
   const long wgs = ((long)g + 3) / 4;
-  long cap = 768;  // persistent workgroups: a wave's weights (registers) and the workgroup's Wb (LDS) are loaded once
-  if (const char* e = tune_env("PASNL_AS_GRID")) cap = atol(e) > 0 ? atol(e) : cap;  // tuning only
+  const long cap = 768;  // persistent workgroups: a wave's weights (registers) and the workgroup's Wb (LDS) are loaded once
   const dim3 grid((unsigned)(wgs < cap ? wgs : cap)), block(256);
   hipStream_t st = pasnl_hip_stream(stream);
 #define PASNL_AS_GO(CBLK)                                                                                                  \
@@ -3336,13 +3197,6 @@ __device__ __forceinline__ f32x16 tail_product(const TailW<PACKED>& W, const flo
   return acc;
 }
 
-#ifdef PASNL_TUNING  // timing ablations of sa_tail (tools/tail_probe.py): bit 0 no tile loads, 1 no stage 1, 2 no stage 2, 3 no stores
-#define TAIL_ABL_PARAM , int abl
-#define TAIL_ABL(bit) (abl & (1 << (bit)))
-#else
-#define TAIL_ABL_PARAM
-#define TAIL_ABL(bit) 0
-#endif
 template <int NW, bool PACKED>  // waves per workgroup = 32-channel output blocks in flight (one per wave): C <= 32 NW
 __global__ __launch_bounds__(NW * 64) void sa_tail_kernel(long rows, int w, int cb, int C, const float* __restrict__ A,
                                                          const float* __restrict__ S, const float* __restrict__ N,
@@ -3350,7 +3204,7 @@ __global__ __launch_bounds__(NW * 64) void sa_tail_kernel(long rows, int w, int 
                                                          const float* __restrict__ Wb, const float* __restrict__ bb,
                                                          const float* __restrict__ Wagg, const float* __restrict__ bagg,
                                                          float* __restrict__ out, const float* __restrict__ xyz3,
-                                                         float* __restrict__ out_cat, const float* __restrict__ res TAIL_ABL_PARAM) {
+                                                         float* __restrict__ out_cat, const float* __restrict__ res) {
   constexpr int RPW = 32 / NW;  // tile rows a wave stages / writes back
   extern __shared__ float lds[];
   float* vt = lds;                         // [C][33]      V^T, then O^T
@@ -3385,41 +3239,39 @@ __global__ __launch_bounds__(NW * 64) void sa_tail_kernel(long rows, int w, int 
         resv[sgm][i] = res[row * C + min(sgm * 64 + lane, C - 1)];
       }
   }
-  if (!TAIL_ABL(0)) {
-    constexpr int STAGE_DEPTH = 4;
-    const int nA = (C + 63) >> 6, nS = (wp + 63) >> 6, nN = N ? (cbp + 63) >> 6 : 0, total = nA + nS + nN;
-    for (int it0 = 0; it0 < total; it0 += STAGE_DEPTH) {
-      float v[STAGE_DEPTH][RPW];
-      int cl[STAGE_DEPTH], width[STAGE_DEPTH];
-      float* dst[STAGE_DEPTH];
+  constexpr int STAGE_DEPTH = 4;
+  const int nA = (C + 63) >> 6, nS = (wp + 63) >> 6, nN = N ? (cbp + 63) >> 6 : 0, total = nA + nS + nN;
+  for (int it0 = 0; it0 < total; it0 += STAGE_DEPTH) {
+    float v[STAGE_DEPTH][RPW];
+    int cl[STAGE_DEPTH], width[STAGE_DEPTH];
+    float* dst[STAGE_DEPTH];
 #pragma unroll
-      for (int d = 0; d < STAGE_DEPTH; ++d) {
-        const int it = min(it0 + d, total - 1);
-        const bool isA = it < nA, isS = !isA && it < nA + nS;
-        const float* __restrict__ src = isA ? A : (isS ? S : N);
-        const int padded = isA ? C : (isS ? wp : cbp), c0 = (isA ? it : (isS ? it - nA : it - nA - nS)) * 64;
-        width[d] = isA ? C : (isS ? w : cb);
-        dst[d] = isA ? vt : (isS ? st : nt_);
-        cl[d] = min(c0 + lane, padded - 1);
-        const int cc = min(cl[d], width[d] - 1);
+    for (int d = 0; d < STAGE_DEPTH; ++d) {
+      const int it = min(it0 + d, total - 1);
+      const bool isA = it < nA, isS = !isA && it < nA + nS;
+      const float* __restrict__ src = isA ? A : (isS ? S : N);
+      const int padded = isA ? C : (isS ? wp : cbp), c0 = (isA ? it : (isS ? it - nA : it - nA - nS)) * 64;
+      width[d] = isA ? C : (isS ? w : cb);
+      dst[d] = isA ? vt : (isS ? st : nt_);
+      cl[d] = min(c0 + lane, padded - 1);
+      const int cc = min(cl[d], width[d] - 1);
 #pragma unroll
-        for (int i = 0; i < RPW; ++i) {
-          const long row = min(row0 + wave * RPW + i, rows - 1);
-          v[d][i] = src[row * width[d] + cc];
-        }
+      for (int i = 0; i < RPW; ++i) {
+        const long row = min(row0 + wave * RPW + i, rows - 1);
+        v[d][i] = src[row * width[d] + cc];
       }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int d = 0; d < STAGE_DEPTH; ++d)
-#pragma unroll
-        for (int i = 0; i < RPW; ++i) dst[d][cl[d] * 33 + wave * RPW + i] = cl[d] < width[d] ? v[d][i] : 0.f;
     }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = 0; d < STAGE_DEPTH; ++d)
+#pragma unroll
+      for (int i = 0; i < RPW; ++i) dst[d][cl[d] * 33 + wave * RPW + i] = cl[d] < width[d] ? v[d][i] : 0.f;
   }
   __syncthreads();
   // ---- stage 1: V^T += relu(Ws^T S^T + bs) + relu(Wb^T N^T + bb); wave = channel block
   const int cbase = wave * 32;
   const bool mine = wave < nblk;
-  if (mine && !TAIL_ABL(1)) {
+  if (mine) {
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = bs[cbase + kappa(i, h)];
@@ -3446,8 +3298,7 @@ __global__ __launch_bounds__(NW * 64) void sa_tail_kernel(long rows, int w, int 
   if (mine) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[i] = bagg[cbase + kappa(i, h)];
-    if (!TAIL_ABL(2))
-      o = tail_product(PACKED ? TailW<PACKED>{Wagg, C, C, h, cbase + l32} : TailW<PACKED>{Wagg + cbase + l32, C, C, h, 0}, vt, l32, o);
+    o = tail_product(PACKED ? TailW<PACKED>{Wagg, C, C, h, cbase + l32} : TailW<PACKED>{Wagg + cbase + l32, C, C, h, 0}, vt, l32, o);
   }
   __syncthreads();  // every wave has read V^T: the tile becomes O^T
   if (mine) {
@@ -3470,7 +3321,7 @@ __global__ __launch_bounds__(NW * 64) void sa_tail_kernel(long rows, int w, int 
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
       const long row = row0 + wave * RPW + i;
-      if (row < rows && c < C && !(TAIL_ABL(3) && v[i] != 12345.f)) out[row * C + c] = v[i];
+      if (row < rows && c < C) out[row * C + c] = v[i];
     }
     if (out_cat) {  // the same rows again as [0 | xyz | O] (C + 4 wide, 16-byte aligned): the next module's concat for free
 #pragma unroll
@@ -3484,11 +3335,6 @@ __global__ __launch_bounds__(NW * 64) void sa_tail_kernel(long rows, int w, int 
 }
 }  // namespace pasnl
 
-#ifdef PASNL_TUNING
-#define TAIL_ABL_ARG , (tune_env("PASNL_TAIL_ABL") ? atoi(tune_env("PASNL_TAIL_ABL")) : 0)
-#else
-#define TAIL_ABL_ARG
-#endif
 static int sa_tail_entry(int rows, int w, int cb, int c, const float* after, const float* skip_max, const float* att,
                          const float* ws, const float* bs, const float* wb, const float* bb, const float* wagg,
                          const float* bagg, float* out, const float* xyz3, float* out_cat, pasnl_stream_t stream,
@@ -3510,7 +3356,7 @@ static int sa_tail_entry(int rows, int w, int cb, int c, const float* after, con
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return PASNL_ELAUNCH;
   hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 31) / 32)), dim3(nw * 64), lds, pasnl_hip_stream(stream), (long)rows, w, cb, c,
-                     after, skip_max, cb ? att : nullptr, ws, bs, wb, bb, wagg, bagg, out, xyz3, out_cat, residual TAIL_ABL_ARG);
+                     after, skip_max, cb ? att : nullptr, ws, bs, wb, bb, wagg, bagg, out, xyz3, out_cat, residual);
   return pasnl_launch_status();
 }
 

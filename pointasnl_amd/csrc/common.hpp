@@ -209,15 +209,8 @@ __device__ __forceinline__ void knn_flag_query(const KnnTieFlags f, int bi, int 
   if (lane == 0) f.flist[(size_t)bi * m + atomicAdd(&f.nflag[bi], 1)] = j;
 }
 
-// Tuning / A-B switches read from the environment exist ONLY in the diagnostic build (make tuning ->
-// libpasnl_hip_tuning.so, never loaded by the package): the product library reads no environment variable and
-// keeps no global state (include/pasnl.h), so a launch is a pure function of its arguments.
-#ifdef PASNL_TUNING
-inline const char* tune_env(const char* name) { return getenv(name); }
-#else
-constexpr const char* tune_env(const char*) { return nullptr; }
-#endif
-
+// The library reads no environment variable and keeps no global state (include/pasnl.h), so a launch is a pure function
+// of its arguments.
 
 // internal launchers behind pasnl_knn_batch / _ws / _tree / _ref (host side; defined in grouping.hip, knn_grid.hip, knn_tree.hip)
 int knn_brute_launch(int b, int n, int m, int k, const float* support, const float* queries, void* idx, int idx_is_i64, float* dist2,

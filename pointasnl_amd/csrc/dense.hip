@@ -201,7 +201,6 @@ static DensePlan dense_plan(int rows, int kdim, int n) {
   if (want > kdim / 64) want = kdim / 64;
   if (want < 1) want = 1;
   p.kchunk = ((kdim + want - 1) / want + 127) & ~127;  // a wave's quarter = whole groups of 4 chunks of 8
-  if (const char* e = tune_env("PASNL_DENSE_KCHUNK")) p.kchunk = atoi(e);  // (tuning build only)
   p.ksplit = (kdim + p.kchunk - 1) / p.kchunk;
   p.counter_bytes = ((size_t)p.ncb * 4 + 255) & ~(size_t)255;
   p.bytes = p.counter_bytes + (p.ksplit > 1 ? (size_t)p.ksplit * p.ncb * p.rb * 1024 * 4 : 0);

@@ -248,16 +248,6 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn_kernel(int n, int m, in
 // ---------------------------------------------------------------------------------------------
 constexpr int KNN2_CAP = 128;  // candidate buffer per query (keys)
 
-// Diagnostic build only (-DPASNL_KNN_PROBE, tools/knn_probe.py): s_memtime marks between the phases, summed over waves
-#ifdef PASNL_KNN_PROBE
-__device__ unsigned long long knn_probe[8];
-#define KNN_MARK(t) do { __builtin_amdgcn_sched_barrier(0); t = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define KNN_PROBE(...) __VA_ARGS__
-#else
-#define KNN_MARK(t)
-#define KNN_PROBE(...)
-#endif
-
 template <int R, int QW, typename IdxT>
 __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, int k, const float* __restrict__ support,
                                                                 const float* __restrict__ queries, IdxT* __restrict__ idx,
@@ -279,7 +269,6 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
     qx[q] = p[0]; qy[q] = p[1]; qz[q] = p[2];
     m1[q] = INF_BITS; m2[q] = INF_BITS;
   }
-  KNN_PROBE(unsigned long long k0, k1, k2, k3, k4; KNN_MARK(k0);)
   // ---- pass 1: per-lane R smallest distances
   for (int base = 0; base < n; base += SEARCH_TILE) {
     int tcnt = min(SEARCH_TILE, n - base);
@@ -301,7 +290,6 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
       }
     }
   }
-  KNN_MARK(k1);
   // ---- bound U = K-th smallest of the lane minima
   uint32_t U[QW];
 #pragma unroll
@@ -316,7 +304,6 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
       if (r == ((k - 1) >> 6)) u = (uint32_t)__builtin_amdgcn_readlane((int)mv[r], (k - 1) & 63);
     U[q] = u;
   }
-  KNN_MARK(k2);
   // ---- pass 2: collect candidates d <= U in index order
   int cnt[QW];
 #pragma unroll
@@ -349,7 +336,6 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
       }
     }
   }
-  KNN_MARK(k3);
   // ---- sort + emit; overflowing queries are flagged for the fallback pass
   bool overflow = false;
 #pragma unroll
@@ -382,13 +368,6 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
       if (flags.nflag && knn_sorted_has_tie(key[0], key[1], k, lane)) knn_flag_query(flags, bi, m, j, lane);
     }
   }
-#ifdef PASNL_KNN_PROBE
-  KNN_MARK(k4);
-  if (lane == 0) {
-    atomicAdd(&knn_probe[0], k1 - k0); atomicAdd(&knn_probe[1], k2 - k1); atomicAdd(&knn_probe[2], k3 - k2);
-    atomicAdd(&knn_probe[3], k4 - k3); atomicAdd(&knn_probe[4], 1ull);
-  }
-#endif
   // ---- fallback (rare): sorted-list insertion for the flagged queries; every wave helps staging the tiles
   if (!__syncthreads_or(overflow ? 1 : 0)) return;
   float tau[QW], tie_tau[QW];  // (tie_tau: knn_kernel's note)
@@ -793,12 +772,10 @@ extern "C" int pasnl_query_ball_point(int b, int n, int m, float radius, int nsa
   constexpr int QW = 4;
   // max(sqrtf(d2),1e-20f) < radius: for radius <= 1e-20f nothing can hit -> threshold 0 (d2 < 0 never true)
   float thr2 = (radius > 1e-20f) ? ball_threshold(radius) : 0.f;
-  // Grid-pruned kernel for LDS-sized clouds (every in-model use and the north-star shape); PASNL_BALL_BRUTE=1 (tuning
-  // build only) forces the brute-force kernel, which also serves larger clouds.
-  if (!tune_env("PASNL_BALL_BRUTE")) {
-    const int rc = ball_grid_launch(b, n, m, radius, thr2, nsample, xyz1, xyz2, idx, pts_cnt, pasnl_hip_stream(stream));
-    if (rc != PASNL_EUNSUPPORTED) return rc;
-  }
+  // Grid-pruned kernel for LDS-sized clouds (every in-model use and the north-star shape); the brute-force kernel below
+  // serves larger clouds.
+  const int rc = ball_grid_launch(b, n, m, radius, thr2, nsample, xyz1, xyz2, idx, pts_cnt, pasnl_hip_stream(stream));
+  if (rc != PASNL_EUNSUPPORTED) return rc;
   size_t lds = (size_t)SEARCH_TILE * 12 + (size_t)SEARCH_WAVES * QW * nsample * sizeof(int);
   PASNL_REQUIRE(lds <= 160 * 1024, PASNL_EUNSUPPORTED);
   auto kern = ball_query_kernel<QW>;
@@ -825,15 +802,6 @@ static int knn_launch(int b, int n, int m, int k, const float* support, const fl
   return pasnl_launch_status();
 }
 
-#ifdef PASNL_KNN_PROBE
-// [pass 1 (incl. staging), bound, pass 2, emit, waves] cycles summed over waves
-extern "C" int pasnl_knn_probe_read(unsigned long long* host8) {
-  if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(pasnl::knn_probe), sizeof(pasnl::knn_probe)) != hipSuccess) return -1;
-  unsigned long long zero[8] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(pasnl::knn_probe), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 extern "C" int pasnl_knn_batch(int b, int n, int m, int k, const float* support, const float* queries, void* idx,
                                int idx_is_i64, float* dist2, pasnl_stream_t stream) {
   return pasnl::knn_brute_launch(b, n, m, k, support, queries, idx, idx_is_i64, dist2, pasnl::KnnTieFlags{nullptr, nullptr},
@@ -850,16 +818,14 @@ int pasnl::knn_brute_launch(int b, int n, int m, int k, const float* support, co
   PASNL_REQUIRE(b <= 65535, PASNL_EUNSUPPORTED);
   // Two-pass selection wins wherever selection dominates (measured: 2.6x at N=1024,K=32; 3.7x at N=512,K=64); for
   // small K over large clouds both kernels are bound by the distance loop and the single pass is ahead
-  // (N=8192,K=16: 795 vs 982 us).  PASNL_KNN_INSERTION=1 forces the insertion kernel (A/B measurements).
-  if (k <= 64 && (!(k <= 16 && n > 2048) || tune_env("PASNL_KNN_TWO_PASS")) && !tune_env("PASNL_KNN_INSERTION")) {
+  // (N=8192,K=16: 795 vs 982 us).
+  if (k <= 64 && !(k <= 16 && n > 2048)) {
     // queries per wave: a wave works through its queries one after the other (two in-wave sorts each), so a launch with few
     // queries is ONE round of long chains (cls layer 2, 8 192 queries at four per wave: 2 048 waves on 1 024 SIMDs, 136 us of
     // which 2/3 are the sorts); fewer queries per wave until the chip holds ~8 waves per SIMD
     const long nq = (long)b * m;
-#ifndef PASNL_KNN2_MIN_WAVES
-#define PASNL_KNN2_MIN_WAVES 8192L
-#endif
-    const int qw = nq >= 4L * PASNL_KNN2_MIN_WAVES ? 4 : (nq >= 2L * PASNL_KNN2_MIN_WAVES ? 2 : 1);
+    constexpr long min_waves = 8192;
+    const int qw = nq >= 4L * min_waves ? 4 : (nq >= 2L * min_waves ? 2 : 1);
     dim3 grid((m + SEARCH_WAVES * qw - 1) / (SEARCH_WAVES * qw), b), block(SEARCH_WAVES * 64);
 #define PASNL_KNN2Q(RR, Q, T) hipLaunchKernelGGL((knn2_kernel<RR, Q, T>), grid, block, 0, st, n, m, k, support, queries, static_cast<T*>(idx), dist2, flags)
 #define PASNL_KNN2(RR, T) { if (qw == 4) PASNL_KNN2Q(RR, 4, T); else if (qw == 2) PASNL_KNN2Q(RR, 2, T); else PASNL_KNN2Q(RR, 1, T); }

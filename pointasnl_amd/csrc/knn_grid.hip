@@ -547,34 +547,18 @@ using namespace pasnl;
 extern "C" int pasnl_knn_batch(int b, int n, int m, int k, const float* support, const float* queries, void* idx,
                                int idx_is_i64, float* dist2, pasnl_stream_t stream);
 
-static int kg_min_n() {
-  if (const char* e = tune_env("PASNL_KNN_GRID_MIN_N")) return atoi(e);  // tuning build only
-  return PASNL_KNN_GRID_MIN_N;
-}
-
 size_t pasnl::knn_grid_ws_bytes(int b, int n) {
-  if (b <= 0 || n < kg_min_n() || n > KG_BUILD_T * KG_PPT) return 0;
+  if (b <= 0 || n < PASNL_KNN_GRID_MIN_N || n > KG_BUILD_T * KG_PPT) return 0;
   return (size_t)b * kg_stride(n);
 }
 extern "C" size_t pasnl_knn_workspace_bytes(int b, int n) { return pasnl::knn_grid_ws_bytes(b, n); }
 
-#ifdef PASNL_TUNING
-extern "C" void pasnl_tuning_stamp(int slot, hipStream_t st);
-#endif
 int pasnl::knn_grid_launch(int b, int n, int m, int k, const float* support, const float* queries, void* idx, int idx_is_i64,
                            float* dist2, void* workspace, size_t workspace_bytes, int max_workgroups, pasnl::KnnTieFlags flags,
                            hipStream_t st) {
   const size_t need = knn_grid_ws_bytes(b, n);
   if (need == 0 || k > 64 || k > n || m <= 0) {  // small clouds / wide lists: the brute-force kernels (same results)
-#ifdef PASNL_TUNING
-    const bool stamp = tune_env("PASNL_STAMP_N") && atoi(tune_env("PASNL_STAMP_N")) == n;  // (tools/step_stamps.py)
-    if (stamp) pasnl_tuning_stamp(6, st);
-    const int rc = knn_brute_launch(b, n, m, k, support, queries, idx, idx_is_i64, dist2, flags, st);
-    if (stamp) pasnl_tuning_stamp(7, st);
-    return rc;
-#else
     return knn_brute_launch(b, n, m, k, support, queries, idx, idx_is_i64, dist2, flags, st);
-#endif
   }
   PASNL_REQUIRE(b >= 0 && n > 0 && m >= 0 && k > 0, PASNL_EINVAL);
   PASNL_REQUIRE(support && queries && idx, PASNL_ENULL);
@@ -584,10 +568,8 @@ int pasnl::knn_grid_launch(int b, int n, int m, int k, const float* support, con
   const size_t stride = kg_stride(n);
   // ~0.4 K records per cell: the sphere of radius h around a query (what ring 1 certifies) then holds ~1.7 K of them
   // target: ~0.7 K records in the cell of a point (measured optimum on uniform-box, ball and lidar-like clouds, K = 16 / 32)
-  float rho = fmaxf(4.f, 0.7f * (float)k);
-  if (const char* e = tune_env("PASNL_KNN_RHO")) rho = (float)atof(e) * (float)k;  // tuning build only
-  int refine = 2;
-  if (const char* e = tune_env("PASNL_KNN_REFINE")) refine = atoi(e);  // tuning build only
+  const float rho = fmaxf(4.f, 0.7f * (float)k);
+  const int refine = 2;
   hipLaunchKernelGGL(knn_grid_build_kernel, dim3(b), dim3(KG_BUILD_T), 0, st, n, rho, refine, support, static_cast<char*>(workspace),
                      stride);
   dim3 grid((m + KG_WAVES - 1) / KG_WAVES, b), block(KG_WAVES * 64);

@@ -9,9 +9,9 @@
 // bit for bit, for data with ties, by re-doing what nanoflann does -- the same tree (divideTree / middleSplit_ / planeSplit,
 // nanoflann.hpp:916-1043, re-stated here with explicit stacks; every float expression in the reference's association, no
 // contraction) and the same search (searchLevel :1351-1410, near child first) -- on the GPU:
-//   * knn_tree_build_lds_kernel (n <= 8192, the points in LDS) / knn_tree_build_par_kernel (n <= 10240, gathers): a workgroup
-//     per cloud builds the tree level by level, a wave per node, with planeSplit's Hoare loop in closed form; knn_tree_build_kernel: the literal one-lane restatement (larger clouds, and the
-//     checker of the parallel build in the tuning build);
+//   * knn_tree_build_lds_kernel (n <= 8192, the points in LDS) or knn_tree_build_big_kernel (larger clouds, the records in the
+//     workspace), then knn_tree_build_deep_kernel for the subtrees they leave: a workgroup builds the tree level by level, a
+//     wave per node, with planeSplit's Hoare loop in closed form;
 //   * knn_tree_search_kernel: one lane per query walks it as a flat state machine, the result set as the k smallest
 //     (distance, arrival) keys in LDS, sorted once at the end.
 //   16 clouds of 8192 points, 1024 queries, k = 32: 60.2 ms (round 3: one lane per cloud) -> 1.1 ms; the canonical-order
@@ -31,7 +31,7 @@ struct KtNode {   // leaf: child1 < 0, a = left, b = right (as int bits); inner:
   float divlow, divhigh;
 };
 
-struct KtFrame {  // one activation of divideTree
+struct KtFrame {  // one activation of divideTree; the workspace keeps KT_DEPTH of them, frame 1's bbox is the root box the searches read
   unsigned left, right, idx;
   int node, cutfeat, phase;
   float cutval;
@@ -70,9 +70,7 @@ constexpr int KTD_MAXWORK = 128;  // subtrees handed to the second phase at most
 constexpr int KTD_TOP = 4;
 constexpr int KTB_WAVES = 16;          // waves of the parallel build's workgroup (one workgroup per cloud)
 constexpr int KTB_LDS_NMAX = 8192;     // points (of a cloud, of a subtree) whose 18-byte records + positions fit the LDS (147 KB)
-constexpr int KTB_LDS_NMAX_ = KTB_LDS_NMAX;
 constexpr int KTD_LDSQ_MAX = 6000;  // points of a subtree whose two level queues still fit in LDS behind its records
-constexpr int KTB_NMAX = 10240;        // points per cloud it holds in LDS (vind + the cut coordinate + a scratch slice)
 static inline int kt_queue_cap(int n) { return n / (KT_LEAF + 1) + 2; }  // inner nodes of one level: more than KT_LEAF points each
 // workspace of one cloud: [flag, root, nodes used, depth] | vind[n] | nodes[2n] | build frames[KT_DEPTH] | 2 level queues |
 // recs[n]: {x, y, z, index} of vind[i] -- the points in LEAF ORDER, so that a leaf's scan is one contiguous read
@@ -82,172 +80,10 @@ static inline size_t kt_recs_offset(int n) {
 }
 static inline size_t kt_cloud_bytes(int n) { return kt_recs_offset(n) + kt_align_h((size_t)n * 16); }
 
-__device__ void knn_tree_build_body(int cloud, int n, const float* __restrict__ pts_all, char* __restrict__ ws_all,
-                                    size_t stride, size_t recs_off) {
-  const float* pts = pts_all + (size_t)cloud * n * 3;
-  char* ws = ws_all + (size_t)cloud * stride;
-  int* hdr = reinterpret_cast<int*>(ws);
-  unsigned* vind = reinterpret_cast<unsigned*>(ws + kt_align(KT_HDR));
-  KtNode* nodes = reinterpret_cast<KtNode*>(ws + kt_align(KT_HDR) + kt_align((size_t)n * 4));
-  KtFrame* st = reinterpret_cast<KtFrame*>(ws + kt_align(KT_HDR) + kt_align((size_t)n * 4) + kt_align((size_t)KT_NNODES(n) * sizeof(KtNode)));
-  hdr[0] = 0;
-  for (int i = 0; i < n; ++i) vind[i] = (unsigned)i;                       // init_vind (:1318)
-  auto get = [&](unsigned idx, int d) { return pts[(size_t)idx * 3 + d]; };  // dataset_get -> kdtree_get_pt
-  // computeBoundingBox (:1321-1346)
-  float root[6];
-  for (int d = 0; d < 3; ++d) root[2 * d] = root[2 * d + 1] = get(0, d);
-  for (int k = 1; k < n; ++k)
-    for (int d = 0; d < 3; ++d) {
-      const float v = get((unsigned)k, d);
-      if (v < root[2 * d]) root[2 * d] = v;
-      if (v > root[2 * d + 1]) root[2 * d + 1] = v;
-    }
-  auto min_max = [&](const unsigned* ind, unsigned count, int el, float& mn, float& mx) {  // computeMinMax (:898-907)
-    mn = get(ind[0], el);
-    mx = mn;
-    for (unsigned i = 1; i < count; ++i) {
-      const float v = get(ind[i], el);
-      if (v < mn) mn = v;
-      if (v > mx) mx = v;
-    }
-  };
-  int nnodes = 0, sp = 0, maxdepth = 0;
-  // root activation
-  st[0].left = 0; st[0].right = (unsigned)n; st[0].phase = 0;
-  for (int i = 0; i < 6; ++i) st[0].bbox[i] = root[i];
-  while (sp >= 0) {
-    KtFrame& f = st[sp];
-    if (f.phase == 0) {
-      f.node = nnodes++;
-      KtNode& nd = nodes[f.node];
-      if (f.right - f.left <= (unsigned)KT_LEAF) {  // leaf (:921-936): its box shrinks to its points
-        nd.child1 = nd.child2 = -1;
-        nd.a = (int)f.left;
-        nd.divlow = __int_as_float((int)f.right);
-        nd.divhigh = 0.f;
-        for (int d = 0; d < 3; ++d) f.bbox[2 * d] = f.bbox[2 * d + 1] = get(vind[f.left], d);
-        for (unsigned k = f.left + 1; k < f.right; ++k)
-          for (int d = 0; d < 3; ++d) {
-            const float v = get(vind[k], d);
-            if (f.bbox[2 * d] > v) f.bbox[2 * d] = v;
-            if (f.bbox[2 * d + 1] < v) f.bbox[2 * d + 1] = v;
-          }
-        --sp;
-        continue;
-      }
-      // middleSplit_ (:966-1005)
-      unsigned* ind = vind + f.left;
-      const unsigned count = f.right - f.left;
-      const float EPS = 0.00001f;
-      float max_span = f.bbox[1] - f.bbox[0];
-      for (int d = 1; d < 3; ++d) {
-        const float span = f.bbox[2 * d + 1] - f.bbox[2 * d];
-        if (span > max_span) max_span = span;
-      }
-      float max_spread = -1.f;
-      int cutfeat = 0;
-      for (int d = 0; d < 3; ++d) {
-        const float span = f.bbox[2 * d + 1] - f.bbox[2 * d];
-        if (span > (1 - EPS) * max_span) {
-          float mn, mx;
-          min_max(ind, count, d, mn, mx);
-          const float spread = mx - mn;
-          if (spread > max_spread) { cutfeat = d; max_spread = spread; }
-        }
-      }
-      const float split_val = (f.bbox[2 * cutfeat] + f.bbox[2 * cutfeat + 1]) / 2;
-      float mn, mx;
-      min_max(ind, count, cutfeat, mn, mx);
-      float cutval;
-      if (split_val < mn) cutval = mn;
-      else if (split_val > mx) cutval = mx;
-      else cutval = split_val;
-      // planeSplit (:1016-1043)
-      unsigned left = 0, right = count - 1, lim1, lim2;
-      for (;;) {
-        while (left <= right && get(ind[left], cutfeat) < cutval) ++left;
-        while (right && left <= right && get(ind[right], cutfeat) >= cutval) --right;
-        if (left > right || !right) break;
-        const unsigned t = ind[left]; ind[left] = ind[right]; ind[right] = t;
-        ++left; --right;
-      }
-      lim1 = left;
-      right = count - 1;
-      for (;;) {
-        while (left <= right && get(ind[left], cutfeat) <= cutval) ++left;
-        while (right && left <= right && get(ind[right], cutfeat) > cutval) --right;
-        if (left > right || !right) break;
-        const unsigned t = ind[left]; ind[left] = ind[right]; ind[right] = t;
-        ++left; --right;
-      }
-      lim2 = left;
-      unsigned index;
-      if (lim1 > count / 2) index = lim1;
-      else if (lim2 < count / 2) index = lim2;
-      else index = count / 2;
-      f.idx = index; f.cutfeat = cutfeat; f.cutval = cutval;
-      nd.a = cutfeat;
-      for (int i = 0; i < 6; ++i) f.lbox[i] = f.bbox[i];
-      f.lbox[2 * cutfeat + 1] = cutval;
-      f.phase = 1;
-      if (sp + 1 >= KT_DEPTH) { hdr[0] = 1; return; }
-      KtFrame& c = st[sp + 1];
-      c.left = f.left; c.right = f.left + index; c.phase = 0;
-      for (int i = 0; i < 6; ++i) c.bbox[i] = f.lbox[i];
-      ++sp;
-      if (sp > maxdepth) maxdepth = sp;
-    } else if (f.phase == 1) {  // child1 has returned: st[sp + 1] holds its frame (node index, tight box)
-      KtFrame& c = st[sp + 1];
-      nodes[f.node].child1 = c.node;
-      for (int i = 0; i < 6; ++i) f.lbox[i] = c.bbox[i];
-      for (int i = 0; i < 6; ++i) f.rbox[i] = f.bbox[i];
-      f.rbox[2 * f.cutfeat] = f.cutval;
-      f.phase = 2;
-      c.left = f.left + f.idx; c.right = f.right; c.phase = 0;
-      for (int i = 0; i < 6; ++i) c.bbox[i] = f.rbox[i];
-      ++sp;
-    } else {  // child2 has returned
-      KtFrame& c = st[sp + 1];
-      KtNode& nd = nodes[f.node];
-      nd.child2 = c.node;
-      for (int i = 0; i < 6; ++i) f.rbox[i] = c.bbox[i];
-      nd.divlow = f.lbox[2 * f.cutfeat + 1];
-      nd.divhigh = f.rbox[2 * f.cutfeat];
-      for (int d = 0; d < 3; ++d) {
-        f.bbox[2 * d] = fminf(f.lbox[2 * d], f.rbox[2 * d]);
-        f.bbox[2 * d + 1] = fmaxf(f.lbox[2 * d + 1], f.rbox[2 * d + 1]);
-      }
-      --sp;
-    }
-  }
-  // root_bbox after divideTree = the tight box of all points (st[0].bbox); findNeighbors uses it (:1045-1061)
-
-
-  KtFrame& out = st[1];
-  for (int i = 0; i < 6; ++i) out.bbox[i] = st[0].bbox[i];
-  {
-    float4* recs = reinterpret_cast<float4*>(ws + recs_off);
-    for (int i = 0; i < n; ++i) recs[i] = make_float4(get(vind[i], 0), get(vind[i], 1), get(vind[i], 2), __int_as_float((int)vind[i]));
-  }
-  hdr[1] = st[0].node;
-  hdr[2] = nnodes;
-  hdr[3] = maxdepth;
-}
-// A grid of at most `b` workgroups walks the clouds.  nflag (pasnl_knn_batch_ref): only the clouds with flagged queries get a
-// tree -- on tie-free batches every workgroup reads a few counters and returns, so the launch has to be CHEAP TO PLACE: a capped
-// grid (the kernels of a forward running beside it hold the LDS these workgroups ask for; one workgroup per cloud of a large
-// batch queued behind them and held the side stream for ~50 us per search, measured: +8 % on the classifier's step)
-__global__ __launch_bounds__(64) void knn_tree_build_kernel(int b, int n, const float* __restrict__ pts_all, char* __restrict__ ws_all,
-                                                           size_t stride, size_t recs_off, const int* __restrict__ nflag) {
-  if (threadIdx.x != 0) return;
-  for (int cloud = blockIdx.x; cloud < b; cloud += gridDim.x)
-    if (!nflag || nflag[cloud] != 0) knn_tree_build_body(cloud, n, pts_all, ws_all, stride, recs_off);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// The same tree, built by a WORKGROUP per cloud (n <= KTB_NMAX).  What makes the serial build slow is not its arithmetic
-// but that one lane walks a chain of dependent global loads (60 ms for 16 clouds of 8192 points); what makes it look
-// inherently serial is planeSplit's in-place Hoare partition.  Both yield:
+// The tree is built by a WORKGROUP.  A literal one-lane restatement of divideTree is slow not for its arithmetic but because
+// one lane walks a chain of dependent global loads (60 ms for 16 clouds of 8192 points); what makes the build look inherently
+// serial is planeSplit's in-place Hoare partition.  Both yield:
 //   * the activations of one tree LEVEL are independent (disjoint slices of vind): a wave per node, level by level, the
 //     nodes of the next level queued in the workspace (breadth first instead of the reference's recursion -- the node
 //     NUMBERS differ, the tree does not, and the search follows child pointers);
@@ -257,11 +93,9 @@ __global__ __launch_bounds__(64) void knn_tree_build_kernel(int b, int n, const 
 //     among the rest (DESCENDING), nothing else has moved, and the pointers meet at c (the `right &&` guard only ever stops
 //     a scan that has nothing left to swap).  Ranks by ballot + prefix popcount, positions through a scratch slice, swaps in
 //     parallel -- the same permutation as the loop, element for element (checked against a transcription of the loop on
-//     200 000 random slices with ties, tests/test_knn_tree_partition.py, and against the serial build on the GPU);
+//     200 000 random slices with ties, tests/test_knn_tree_partition.py);
 //   * the tight box a child returns is the bounding box of its points, so divlow / divhigh (:956-957) are the maximum of
 //     the left part / the minimum of the right part along the cut dimension -- two more reductions, no second traversal.
-// The cut coordinate of a node's points sits in LDS next to vind and is permuted with it; the other coordinates are read
-// from global memory (L2) for the candidate dimensions of middleSplit_ only.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ktb_wave_sync() {  // LDS operations of a wave execute in order; keep the compiler from moving them
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -269,231 +103,8 @@ __device__ __forceinline__ void ktb_wave_sync() {  // LDS operations of a wave e
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ void knn_tree_build_par_body(int cloud, int n, const float* __restrict__ pts_all, char* __restrict__ ws_all, size_t stride,
-                                        size_t recs_off, int stop_level) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned* vind = reinterpret_cast<unsigned*>(smem);                       // [n]
-  float* vals = reinterpret_cast<float*>(vind + n);                          // [n] cut coordinate of vind[i] (current node)
-  unsigned short* sc = reinterpret_cast<unsigned short*>(vals + n);          // [n] positions of misplaced elements
-  float* part = reinterpret_cast<float*>(sc + ((n + 1) & ~1));               // [KTB_WAVES][6] root-box partials
-  int* ctr = reinterpret_cast<int*>(part + KTB_WAVES * 6);                   // [0], [1]: queue lengths; [2]: nodes used; [3]: flag
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* pts = pts_all + (size_t)cloud * n * 3;
-  char* ws = ws_all + (size_t)cloud * stride;
-  int* hdr = reinterpret_cast<int*>(ws);
-  unsigned* gvind = reinterpret_cast<unsigned*>(ws + kt_align(KT_HDR));
-  KtNode* nodes = reinterpret_cast<KtNode*>(ws + kt_align(KT_HDR) + kt_align((size_t)n * 4));
-  KtFrame* fr = reinterpret_cast<KtFrame*>(ws + kt_align(KT_HDR) + kt_align((size_t)n * 4) + kt_align((size_t)KT_NNODES(n) * sizeof(KtNode)));
-  const int qcap = n / (KT_LEAF + 1) + 2;
-  KtWork* queue[2];
-  queue[0] = reinterpret_cast<KtWork*>(reinterpret_cast<char*>(fr) + kt_align((size_t)KT_DEPTH * sizeof(KtFrame)));
-  queue[1] = reinterpret_cast<KtWork*>(reinterpret_cast<char*>(queue[0]) + kt_align((size_t)qcap * sizeof(KtWork)));
-  const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));  // lanes below this one
-
-  // init_vind (:1318), computeBoundingBox (:1321-1346)
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int i = tid; i < n; i += KTB_WAVES * 64) {
-    vind[i] = (unsigned)i;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const float v = pts[(size_t)i * 3 + d];
-      lo[d] = v < lo[d] ? v : lo[d];
-      hi[d] = v > hi[d] ? v : hi[d];
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < 3; ++d) { lo[d] = wave_min_f32(lo[d]); hi[d] = wave_max_f32(hi[d]); }
-  if (lane == 0) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) { part[wave * 6 + 2 * d] = lo[d]; part[wave * 6 + 2 * d + 1] = hi[d]; }
-  }
-  if (tid < 4) ctr[tid] = 0;
-  __syncthreads();
-  float root[6];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    float l = part[2 * d], h = part[2 * d + 1];
-    for (int w = 1; w < KTB_WAVES; ++w) { l = fminf(l, part[w * 6 + 2 * d]); h = fmaxf(h, part[w * 6 + 2 * d + 1]); }
-    root[2 * d] = l; root[2 * d + 1] = h;
-  }
-  if (tid == 0) {
-    ctr[2] = 1;  // node 0 = the root
-    if (n <= KT_LEAF) {
-      nodes[0].child1 = nodes[0].child2 = -1; nodes[0].a = 0; nodes[0].divlow = __int_as_float(n); nodes[0].divhigh = 0.f;
-    } else {
-      KtWork w0; w0.node = 0; w0.left = 0; w0.right = (unsigned)n;
-      for (int i = 0; i < 6; ++i) w0.box[i] = root[i];
-      queue[0][0] = w0;
-      ctr[0] = 1;
-    }
-    for (int i = 0; i < 6; ++i) fr[1].bbox[i] = root[i];  // root_bbox after divideTree = the tight box of all points (what the search reads)
-  }
-  __threadfence_block();
-  __syncthreads();
-
-  int cur = 0, level = 0;
-  for (;;) {
-    const int nq = ctr[cur];
-    if (nq == 0) break;
-    if (stop_level > 0 && level >= stop_level) {
-      // hand the pending subtrees to knn_tree_build_deep_kernel (one workgroup each, records in LDS) -- unless one of them is
-      // too large for its LDS (a very lopsided tree): then this kernel finishes the tree itself
-      if (tid == 0) {
-        int big = 0;
-        for (int e = 0; e < nq; ++e) {
-          const volatile KtWork* qe = queue[cur] + e;
-          big |= (qe->right - qe->left) > (unsigned)KTB_LDS_NMAX_ ? 1 : 0;
-        }
-        ctr[3] |= big << 1;
-      }
-      __syncthreads();
-      if ((ctr[3] & 2) == 0) break;
-      stop_level = 0;
-    }
-    if (level + 2 >= KT_DEPTH) { if (tid == 0) ctr[3] = 1; break; }  // deeper than the search's stack: flagged, not built
-    for (int e = wave; e < nq; e += KTB_WAVES) {
-      const KtWork wk = kt_load_work(queue[cur] + e, lane);
-      const unsigned left = wk.left, right = wk.right, count = right - left;
-      // ---- middleSplit_ (:966-1005)
-      const float EPS = 0.00001f;
-      float max_span = wk.box[1] - wk.box[0];
-      for (int d = 1; d < 3; ++d) {
-        const float span = wk.box[2 * d + 1] - wk.box[2 * d];
-        if (span > max_span) max_span = span;
-      }
-      float max_spread = -1.f, mn_c = 0.f, mx_c = 0.f;
-      int cutfeat = 0;
-      for (int d = 0; d < 3; ++d) {
-        const float span = wk.box[2 * d + 1] - wk.box[2 * d];
-        if (span > (1 - EPS) * max_span) {
-          float mn = INFINITY, mx = -INFINITY;  // computeMinMax (:898-907)
-          for (unsigned p = lane; p < count; p += 64) {
-            const float v = pts[(size_t)vind[left + p] * 3 + d];
-            mn = v < mn ? v : mn;
-            mx = v > mx ? v : mx;
-          }
-          mn = wave_min_f32(mn); mx = wave_max_f32(mx);
-          const float spread = mx - mn;
-          if (spread > max_spread) { cutfeat = d; max_spread = spread; mn_c = mn; mx_c = mx; }
-        }
-      }
-      // (selects, not wk.box[2 * cutfeat]: a dynamically indexed local array lives in scratch memory)
-      const float blo = cutfeat == 0 ? wk.box[0] : (cutfeat == 1 ? wk.box[2] : wk.box[4]);
-      const float bhi = cutfeat == 0 ? wk.box[1] : (cutfeat == 1 ? wk.box[3] : wk.box[5]);
-      const float split_val = (blo + bhi) / 2;
-      float cutval;  // (the second computeMinMax of the reference, on cutfeat, returns mn_c / mx_c again)
-      if (split_val < mn_c) cutval = mn_c;
-      else if (split_val > mx_c) cutval = mx_c;
-      else cutval = split_val;
-      for (unsigned p = lane; p < count; p += 64) vals[left + p] = pts[(size_t)vind[left + p] * 3 + cutfeat];
-      ktb_wave_sync();
-      // ---- planeSplit (:1016-1043): two passes, each the parallel form of the Hoare loop (header)
-      unsigned lim[2];
-      unsigned lo_p = 0;
-#pragma unroll 1
-      for (int pass = 0; pass < 2; ++pass) {
-        auto pred = [&](float v) { return pass == 0 ? v < cutval : v <= cutval; };
-        unsigned cnt = 0;
-        for (unsigned p0 = lo_p; p0 < count; p0 += 64) {
-          const unsigned p = p0 + lane;
-          cnt += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p < count && pred(vals[left + p])));
-        }
-        const unsigned mid = lo_p + cnt;  // where the pointers meet
-        unsigned nl = 0, nr = 0;
-        for (unsigned p0 = lo_p; p0 < mid; p0 += 64) {  // violators among the first cnt positions, ascending
-          const unsigned p = p0 + lane;
-          const bool mis = p < mid && !pred(vals[left + p]);
-          const unsigned long long mk = __builtin_amdgcn_ballot_w64(mis);
-          if (mis) sc[left + lo_p + nl + (unsigned)__builtin_popcountll(mk & lt_mask)] = (unsigned short)p;
-          nl += (unsigned)__builtin_popcountll(mk);
-        }
-        for (unsigned q0 = 0; mid + q0 < count; q0 += 64) {  // satisfiers among the rest, descending
-          const unsigned q = q0 + lane;
-          const bool in = mid + q < count;
-          const unsigned p = count - 1 - (in ? q : 0);
-          const bool mis = in && pred(vals[left + p]);
-          const unsigned long long mk = __builtin_amdgcn_ballot_w64(mis);
-          if (mis) sc[right - 1 - (nr + (unsigned)__builtin_popcountll(mk & lt_mask))] = (unsigned short)p;
-          nr += (unsigned)__builtin_popcountll(mk);
-        }
-        ktb_wave_sync();
-        for (unsigned i = lane; i < nl; i += 64) {  // nl == nr
-          const unsigned a = left + sc[left + lo_p + i], b = left + sc[right - 1 - i];
-          const unsigned ta = vind[a], tb = vind[b];
-          const float va = vals[a], vb = vals[b];
-          vind[a] = tb; vind[b] = ta;
-          vals[a] = vb; vals[b] = va;
-        }
-        ktb_wave_sync();
-        lim[pass] = mid;
-        lo_p = mid;
-      }
-      unsigned index;
-      if (lim[0] > count / 2) index = lim[0];
-      else if (lim[1] < count / 2) index = lim[1];
-      else index = count / 2;
-      // ---- the children's tight boxes along cutfeat: divlow = max of the left part, divhigh = min of the right part (:956-957)
-      float dl = -INFINITY, dh = INFINITY;
-      for (unsigned p = lane; p < count; p += 64) {
-        const float v = vals[left + p];
-        if (p < index) dl = v > dl ? v : dl;
-        else dh = v < dh ? v : dh;
-      }
-      dl = wave_max_f32(dl); dh = wave_min_f32(dh);
-      if (lane == 0) {
-        int child[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const unsigned cl = c == 0 ? left : left + index, cr = c == 0 ? left + index : right;
-          const int id = atomicAdd(&ctr[2], 1);
-          child[c] = id;
-          if (cr - cl <= (unsigned)KT_LEAF) {  // leaf (:921-936)
-            nodes[id].child1 = nodes[id].child2 = -1;
-            nodes[id].a = (int)cl;
-            nodes[id].divlow = __int_as_float((int)cr);
-            nodes[id].divhigh = 0.f;
-          } else {
-            KtWork w;
-            w.node = id; w.left = cl; w.right = cr;
-            // left child: high = cutval (:946-947); right child: low = cutval (:951-952)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) w.box[i] = (i == 2 * cutfeat + 1 - c) ? cutval : wk.box[i];
-            queue[cur ^ 1][atomicAdd(&ctr[cur ^ 1], 1)] = w;
-          }
-        }
-        KtNode nd;
-        nd.child1 = child[0]; nd.child2 = child[1]; nd.a = cutfeat; nd.divlow = dl; nd.divhigh = dh;
-        nodes[wk.node] = nd;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (tid == 0) ctr[cur] = 0;
-    cur ^= 1;
-    ++level;
-    __syncthreads();
-  }
-  __syncthreads();
-  float4* recs = reinterpret_cast<float4*>(ws + recs_off);
-  for (int i = tid; i < n; i += KTB_WAVES * 64) {
-    const unsigned v = vind[i];
-    gvind[i] = v;
-    recs[i] = make_float4(pts[(size_t)v * 3], pts[(size_t)v * 3 + 1], pts[(size_t)v * 3 + 2], __int_as_float((int)v));
-  }
-  if (tid == 0) { hdr[0] = ctr[3] & 1; hdr[1] = 0; hdr[2] = ctr[2]; hdr[3] = level; hdr[4] = (ctr[3] & 1) || stop_level == 0 ? 0 : ctr[cur]; hdr[5] = cur; hdr[6] = level; }
-}
-__global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_build_par_kernel(int b, int n, const float* __restrict__ pts_all,
-                                                                           char* __restrict__ ws_all, size_t stride, size_t recs_off, int stop_level,
-                                                                           const int* __restrict__ nflag) {
-  for (int cloud = blockIdx.x; cloud < b; cloud += gridDim.x) {  // (a capped grid walks the clouds: knn_tree_build_kernel's note)
-    if (nflag && nflag[cloud] == 0) continue;
-    knn_tree_build_par_body(cloud, n, pts_all, ws_all, stride, recs_off, stop_level);
-    __syncthreads();  // the next cloud re-uses the LDS
-  }
-}
-
-// The same build with the POINTS in LDS (n <= KTB_LDS_NMAX): records {x, y, z, index} that move with the index list, so every
-// pass over a node is a sequential LDS read.  In the kernel above a pass gathers pts[vind[i]] from global memory, one dependent
+// The build with the POINTS in LDS (n <= KTB_LDS_NMAX): records {x, y, z, index} that move with the index list, so every
+// pass over a node is a sequential LDS read, where a build that gathers pts[vind[i]] from global memory waits one dependent
 // round trip per 64 points.  16 x 8192: 556 -> 485 us -- what remains is one wave's ~9 passes over a large node at the top
 // levels and ~3.5 us of fixed cost per node at the deep ones (EXPERIMENTS.md).
 // One inner node of the build with the points in LDS (middleSplit_ + planeSplit + the children's tight bounds), by one wave:
@@ -829,10 +440,7 @@ __device__ __forceinline__ KtSplit ktb_split_node_wg(float4* rec, PosT* sc, floa
   r.cutfeat = cutfeat; r.cutval = cutval; r.index = index; r.dl = dl; r.dh = dh;
   return r;
 }
-#ifndef KT_COOP_MIN_V
-#define KT_COOP_MIN_V 4096  // measured (16 x 8192 self-kNN, 4 flagged clouds): 1024: 576 us, 2048: 518, 4096: 484, never: 505
-#endif
-constexpr unsigned KT_COOP_MIN = KT_COOP_MIN_V;
+constexpr unsigned KT_COOP_MIN = 4096;  // measured (16 x 8192 self-kNN, 4 flagged clouds): 1024: 576 us, 2048: 518, 4096: 484, never: 505
 constexpr unsigned KT_COOP_FEW = 768;  // ... in a level of at most two nodes  // nodes above this many points are split by the whole workgroup, one after the other
 // ... as a real CALL in the kernels that also hold the one-wave forms (inlined there, the three forms together need more than the 128
 // registers a 1024-thread workgroup has: 140 bytes of scratch per lane, the deep kernel 132 -> 395 us); a large node is
@@ -978,10 +586,14 @@ __device__ void knn_tree_build_lds_body(int cloud, int n, const float* __restric
   }
   if (tid == 0) { hdr[0] = ctr[3]; hdr[1] = 0; hdr[2] = ctr[2]; hdr[3] = level; hdr[4] = ctr[3] ? 0 : ctr[cur]; hdr[5] = cur; hdr[6] = level; }
 }
+// A grid of at most `b` workgroups walks the clouds.  nflag (pasnl_knn_batch_ref): only the clouds with flagged queries get a
+// tree -- on tie-free batches every workgroup reads a few counters and returns, so the launch has to be CHEAP TO PLACE: a capped
+// grid (the kernels of a forward running beside it hold the LDS these workgroups ask for; one workgroup per cloud of a large
+// batch queued behind them and held the side stream for ~50 us per search, measured: +8 % on the classifier's step)
 __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_build_lds_kernel(int b, int n, const float* __restrict__ pts_all,
                                                                            char* __restrict__ ws_all, size_t stride, size_t recs_off, int stop_level,
                                                                            const int* __restrict__ nflag) {
-  for (int cloud = blockIdx.x; cloud < b; cloud += gridDim.x) {  // (a capped grid walks the clouds: knn_tree_build_kernel's note)
+  for (int cloud = blockIdx.x; cloud < b; cloud += gridDim.x) {
     if (nflag && nflag[cloud] == 0) continue;
     knn_tree_build_lds_body(cloud, n, pts_all, ws_all, stride, recs_off, stop_level);
     __syncthreads();  // the next cloud re-uses the LDS
@@ -1448,7 +1060,7 @@ __device__ void knn_tree_search_body(int bi, int blk, int n, int m, int k, const
     rk[bp * 64] = 0xFFFFFFFFu;
   }
 }
-// one wave per workgroup; a capped grid walks the (cloud, block of 64 queries) pairs (knn_tree_build_kernel's note)
+// one wave per workgroup; a capped grid walks the (cloud, block of 64 queries) pairs (knn_tree_build_lds_kernel's note)
 template <typename IdxT>
 __global__ __launch_bounds__(64) void knn_tree_search_kernel(int b, int n, int m, int k, const float* __restrict__ queries,
                                                             const char* __restrict__ ws_all, size_t stride, size_t recs_off,
@@ -1634,14 +1246,6 @@ __global__ __launch_bounds__(KTW_WAVES * 64) void knn_tree_search_wave_kernel(in
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int KTS_NMAX = 2048;
 #define KTS_NNODES(n) (2 * (n) + 32)  // (one id range: the whole tree is built by one workgroup)
-#ifdef PASNL_TUNING
-// phase probe of the FIRST flagged cloud a workgroup takes (tools/knn_small_probe.py): s_memtime at [0] entry, [1] records + box in
-// LDS, [2 + l] level l done (l < 20), [30] build done, [31] searches done
-__device__ unsigned long long kts_probe[32];
-#define KTS_MARK(i) do { if (tid == 0 && blockIdx.x == kts_first) kts_probe[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define KTS_MARK(i) do { } while (0)
-#endif
 // ---------------------------------------------------------------------------------------------------------------------
 // Tie paths (round 6): what the tree search DOES to a listed query's row, without the search.
 //
@@ -1663,17 +1267,6 @@ __device__ unsigned long long kts_probe[32];
 // 8192-point one (225 + the search).  More than KTP_MAXQ listed queries in the batch, more than KTP_TMAX tied points for a
 // query (lattices, padded clouds), more than KTP_MAXW splits: the cloud goes to the full build and search below (`nwork`).
 // ---------------------------------------------------------------------------------------------------------------------
-#ifdef PASNL_TUNING
-// phase probe of workgroup 0 (tools/tie_path_probe.py): s_memtime at [0] entry, [1] the listed queries counted, [2] records + box in
-// LDS, [3] the tied points listed, [4 + i] split i done (i < 24), [30] the row written
-#define KTP_MARK(i) do { if (threadIdx.x == 0 && S->probe != 0) kts_probe[i] = __builtin_amdgcn_s_memtime(); } while (0)  // (S->probe: LDS; a flag in global memory costs a mark ~1 us)
-__device__ unsigned long long ktp_wg_cycles[64];  // (knn_tie_path_kernel: cycles and final code of each listed cloud's workgroup, tools/tie_path_l2.py)
-__device__ int ktp_paths[8];       // clouds by the form that took them: [0] sets only, [1] records moved, [2] tree + search, [3] return code 1 of the set form, [4] code 2
-#define KTP_COUNT(i) do { if (threadIdx.x == 0) atomicAdd(&ktp_paths[i], 1); } while (0)
-#else
-#define KTP_MARK(i) do { } while (0)
-#define KTP_COUNT(i) do { } while (0)
-#endif
 constexpr int KTP_MAXQ = 32;    // listed queries per batch this form takes (a workgroup each)
 constexpr int KTP_TMAX = 64;    // tied points of one query (a lane each)
 constexpr int KTP_MAXW = 32;    // nodes split for one cloud's listed queries
@@ -1702,7 +1295,7 @@ struct KtpShared {
   union { KtpWork work[KTP_MAXW]; KtiWork iwork[KTP_MAXW]; };
   KtSplit split;
   int nmem, nw, ncur, bad;
-  int cloud, entry, probe, npts;
+  int cloud, entry, spare, npts;  // (spare: an unused word that keeps the layout)
   int stage, cutfeat, adv;  // the set form's pass over the current node: -1 fresh, 0 min / max of all dimensions, 1 the cut at the box's middle, 2 at the points' edge
   float cutval;
   int wsum[KTB_WAVES];
@@ -2116,7 +1709,6 @@ __device__ __forceinline__ int ktp_descend_records(float4* rec, unsigned short* 
       }
     }
     __syncthreads();
-    if (cur < 24) KTP_MARK(4 + cur);
     if (S->bad != 0) return 1;
   }
   // a run in arrival order: (key, position) ascending, from the run's first slot on; what does not fit the row is dropped
@@ -2135,7 +1727,6 @@ __device__ __forceinline__ int ktp_descend_records(float4* rec, unsigned short* 
     if (lane < t && slot < k) out_c[(size_t)S->qj[m_grp >> 8] * k + slot] = (IdxT)S->mem_idx[ml];
   }
   __syncthreads();
-  KTP_MARK(30);
   return 0;
 }
 
@@ -2228,7 +1819,6 @@ __device__ __forceinline__ int ktp_resolve_cloud(const float4* rec, const float*
   }
   __syncthreads();
   const int t = S->nmem;
-  KTP_MARK(3);
   if (S->bad != 0 || t > KTP_TMAX) return 1;
   // More than K candidates at or within a few ulps above the K-th distance (a run that reaches beyond the row's end, a (K+1)-th
   // point next to the K-th): WHICH of them the reference keeps can hinge on the rounding of its pruning bound (mindistsq + cut_dist -
@@ -2280,7 +1870,7 @@ __device__ __forceinline__ int ktp_resolve_cloud(const float4* rec, const float*
   }
   __syncthreads();
   if (S->bad != 0) return S->bad;  // (uniform)
-  int cur = 0, npass = 0;
+  int cur = 0;
   for (;;) {
     if (cur >= S->nw) break;  // (uniform: written before the last barrier)
     // (the node stays in LDS: an index that is not a constant -- box[2 * cutfeat] -- would send a copy in registers to scratch memory)
@@ -2432,8 +2022,6 @@ __device__ __forceinline__ int ktp_resolve_cloud(const float4* rec, const float*
       if (lane == 0) { S->adv = adv; if (fail != 0) S->bad = fail; }
     }
     __syncthreads();
-    if (npass < 24) KTP_MARK(4 + npass);
-    ++npass;
     if (S->bad != 0) return S->bad;
     cur += S->adv;
   }
@@ -2450,7 +2038,6 @@ __device__ __forceinline__ int ktp_resolve_cloud(const float4* rec, const float*
     if (lane < t && slot < k) out_c[(size_t)S->qj[m_grp >> 8] * k + slot] = (IdxT)m_idx;
   }
   __syncthreads();
-  KTP_MARK(30);
   return 0;
 }
 
@@ -2469,11 +2056,6 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tie_path_kernel(int b, int
   KtpShared* S = reinterpret_cast<KtpShared*>(red + KTP_RED_WORDS);
   __shared__ float rootbox[6];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef PASNL_TUNING
-  if (tid == 0) S->probe = blockIdx.x == 0 ? 1 : 0;
-  __syncthreads();
-#endif
-  KTP_MARK(0);
   // the batch's listed CLOUDS, numbered thread-major (every workgroup computes the same numbering)
   int cnt = 0;
   for (int c = tid; c < b; c += T) cnt += nflag[c] != 0 ? 1 : 0;
@@ -2491,7 +2073,6 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tie_path_kernel(int b, int
     return;
   }
   const int excl = base + incl - cnt;
-  KTP_MARK(1);
   for (int g = blockIdx.x; g < total; g += gridDim.x) {
     __syncthreads();
     if (g >= excl && g < excl + cnt) {  // (one thread)
@@ -2504,29 +2085,18 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tie_path_kernel(int b, int
     }
     __syncthreads();
     const int cloud = S->cloud, nq = nflag[cloud];
-#ifdef PASNL_TUNING
-    const unsigned long long ktp_t0 = __builtin_amdgcn_s_memtime();
-#endif
     if (nq > ktp_max_queries(k)) {  // (uniform) a cloud of many ties: the full build
       if (tid == 0) atomicExch(&nwork[cloud], nq);
       continue;
     }
     const float* pts = pts_all + (size_t)cloud * n * 3;
     kts_load_records<!GLOBAL>(pts, n, rec, red, rootbox, tid);
-    KTP_MARK(2);
     int rc = ktp_resolve_cloud<IdxT, GLOBAL>(rec, pts, red, S, rootbox, n, k, nq, flist + (size_t)cloud * m, queries + (size_t)cloud * m * 3,
                                              out + (size_t)cloud * m * k, tid);
-    if (rc == 0) KTP_COUNT(0);
-    if (rc == 1) KTP_COUNT(3);
-    if (rc == 2) KTP_COUNT(4);
     if (rc == 2 && !GLOBAL) {  // two tied points in one leaf (duplicated points), or a split among equal coordinates: the form that moves the records
       rc = ktp_descend_records<IdxT>(rec, sc, red, S, rootbox, n, k, out + (size_t)cloud * m * k, tid);
-      if (rc == 0) KTP_COUNT(1);
     }
     if (rc != 0 && tid == 0) atomicExch(&nwork[cloud], nq);  // every listed query of the cloud, the done ones too (rows are simply written again)
-#ifdef PASNL_TUNING
-    if (tid == 0 && g < 32) { ktp_wg_cycles[g] = __builtin_amdgcn_s_memtime() - ktp_t0; ktp_wg_cycles[32 + g] = (unsigned long long)(rc + 10 * S->npts + 1000 * S->nmem); }
-#endif
   }
 }
 
@@ -2556,24 +2126,9 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_small_kernel(int b, i
   KtpShared* S = reinterpret_cast<KtpShared*>(red + KTS_RED_WORDS);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-#ifdef PASNL_TUNING
-  // (the first listed cloud, found by the whole workgroup: one thread reading the counters one after the other cost every launch of
-  // the tuning build ~30 us and misled a round of experiments)
-  __shared__ int kts_first_s;
-  if (tid == 0) kts_first_s = 0x7fffffff;
-  __syncthreads();
-  for (int c = tid; c < b; c += KTB_WAVES * 64) if (nflag[c] != 0) atomicMin(&kts_first_s, c);
-  __syncthreads();
-  const int kts_first = kts_first_s == 0x7fffffff ? -1 : kts_first_s % (int)gridDim.x;
-#endif
-#ifdef PASNL_TUNING
-  if (tid == 0) S->probe = blockIdx.x == kts_first ? 1 : 0;
-  __syncthreads();
-#endif
   for (int cloud = blockIdx.x; cloud < b; cloud += gridDim.x) {
     const int nq = nflag[cloud];
     if (nq == 0) continue;  // (uniform)
-    KTS_MARK(0);
     const float* pts = pts_all + (size_t)cloud * n * 3;
     // A FEW listed queries (chance ties): their runs of equal distances put in arrival order along the tree paths that separate them
     // (ktp_resolve_cloud: ~10 us where tree + search take 85); anything it does not take: the tree and the searches below
@@ -2583,19 +2138,14 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_small_kernel(int b, i
       const int rc = ktp_resolve_cloud<IdxT>(rec, pts, red, S, rootbox, n, k, nq, flist + (size_t)cloud * m, queries + (size_t)cloud * m * 3,
                                             out + (size_t)cloud * m * k, tid);
       resolved = rc == 0;
-      if (rc == 0) KTP_COUNT(0);
-      if (rc == 1) KTP_COUNT(3);
-      if (rc == 2) KTP_COUNT(4);
       // 2: two tied points in one leaf -- duplicated points --, or a split among equal coordinates.  The form that moves the records walks
       // one chain of ~8 splits per leaf involved (~50 us), the tree + parallel searches below take 85-120: it pays for one or two
       // leaves -- at most four distinct tied points, however many queries list them (a duplicated pair lists a dozen)
       if (rc == 2 && S->npts <= 4) {
         resolved = ktp_descend_records<IdxT>(rec, sc, red, S, rootbox, n, k, out + (size_t)cloud * m * k, tid) == 0;
-        if (resolved) KTP_COUNT(1);
       }
     }
-    if (resolved) { KTS_MARK(31); continue; }  // (uniform)
-    KTP_COUNT(2);
+    if (resolved) continue;  // (uniform)
     kts_load_records(pts, n, rec, part, rootbox, tid);
     if (tid < 4) ctr[tid] = 0;
     __syncthreads();
@@ -2611,7 +2161,6 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_small_kernel(int b, i
       }
     }
     __syncthreads();
-    KTS_MARK(1);
     int cur = 0, level = 0;
     for (;;) {
       const int nqn = ctr[cur];
@@ -2654,10 +2203,8 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_small_kernel(int b, i
       cur ^= 1;
       ++level;
       __syncthreads();
-      if (level < 20) KTS_MARK(1 + level);
     }
     __syncthreads();
-    KTS_MARK(30);
     if (ctr[3] != 0) {  // deeper than the search's stack: flagged, the rows keep the canonical order
       if (tid == 0) atomicExch(flag, 1);
     } else {
@@ -2669,7 +2216,6 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_small_kernel(int b, i
           atomicExch(flag, 1);
       }
     }
-    KTS_MARK(31);
     __syncthreads();  // the next cloud re-uses the LDS
   }
 }
@@ -2970,7 +2516,8 @@ __device__ __forceinline__ bool ktl_expand_small(const float* __restrict__ pts, 
 
 // the same split by ONE wave (the searching one) for nodes of at most KTL_WAVE_MAX points: the ~50 small nodes a search reaches cost
 // ~12 us each through the workgroup form (a dozen barriers of sixteen waves); the trips of one wave over <= 512 points are cheaper.
-// The code of knn_tree_build_par_body's wave-per-node split on the (index list, cut coordinate) pair.
+// The index list and the cut coordinate of each point sit in LDS and are permuted together; the other coordinates are read from
+// global memory for the candidate dimensions of middleSplit_ only.
 constexpr unsigned KTL_WAVE_MAX = 512;
 __device__ __forceinline__ bool ktl_expand_wave(const float* __restrict__ pts, unsigned* vind, float* vals, unsigned short* sc,
                                                 KtlNode* nodes, int* ctl, const int nid, const int lane) {
@@ -3281,15 +2828,12 @@ __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_lazy_kernel(int b, in
 }  // namespace pasnl
 
 using namespace pasnl;
-#ifdef PASNL_TUNING
-extern "C" void pasnl_tuning_stamp(int slot, hipStream_t st);
-#endif
 
 // LDS of a subtree's workgroup: records + scratch positions (18 bytes per point) for a subtree of up to min(n, KTB_LDS_NMAX)
 // points (the first phase keeps larger ones to itself), or those of KTD_LDSQ_MAX points plus their two level queues --
 // whichever is larger
 static int knn_tree_deep_launch(int b, int n, char* clouds, size_t stride, size_t recs_off, const int* nflag, hipStream_t st) {
-  const int grid = nflag ? std::min(b * 16, 64) : b * 16;  // the pending subtrees are dealt to the grid; capped under _ref (knn_tree_build_kernel's note)
+  const int grid = nflag ? std::min(b * 16, 64) : b * 16;  // the pending subtrees are dealt to the grid; capped under _ref (knn_tree_build_lds_kernel's note)
   using namespace pasnl;
   const size_t cmax = (size_t)(n < KTB_LDS_NMAX ? n : KTB_LDS_NMAX);
   const size_t c = cmax < (size_t)KTD_LDSQ_MAX ? cmax : (size_t)KTD_LDSQ_MAX;
@@ -3337,44 +2881,25 @@ int pasnl::knn_tree_launch(int b, int n, int m, int k, const float* support, con
     hipLaunchKernelGGL(knn_tree_clear_kernel, dim3(1), dim3(64), 0, st, flag);
   }
   const int* nflag = only.nflag;
-  // under _ref the kernels are launched whatever the counts are: capped grids that walk the work (knn_tree_build_kernel's note)
+  // under _ref the kernels are launched whatever the counts are: capped grids that walk the work (knn_tree_build_lds_kernel's note)
   const int bgrid = nflag ? std::min(b, 32) : b;
   char* clouds = base + 256;
   const size_t stride = kt_cloud_bytes(n);
-  const bool serial = tune_env("PASNL_KNN_TREE_SERIAL") != nullptr;  // (tuning build: the one-lane transcription, the checker of the parallel builds)
   const size_t recs_off = kt_recs_offset(n);
-  if (!serial && (n > KTB_LDS_NMAX || tune_env("PASNL_KNN_TREE_BIG")) && !(n <= KTB_NMAX && tune_env("PASNL_KNN_TREE_GATHER"))) {
+  if (n > KTB_LDS_NMAX) {
     // records in the workspace, large nodes by the whole workgroup, then one workgroup per LDS-sized subtree
     hipLaunchKernelGGL(knn_tree_build_big_kernel, dim3(bgrid), dim3(KTB_WAVES * 64), 0, st, b, n, support, clouds, stride, recs_off, nflag);
-    const int rc = knn_tree_deep_launch(b, n, clouds, stride, recs_off, nflag, st);
-    if (rc != PASNL_OK) return rc;
-  } else if (serial) {
-    hipLaunchKernelGGL(knn_tree_build_kernel, dim3(bgrid), dim3(64), 0, st, b, n, support, clouds, stride, recs_off, nflag);
-  } else if (n <= KTB_LDS_NMAX && tune_env("PASNL_KNN_TREE_GATHER") == nullptr) {  // (tuning build: A/B against the gathering build)
+  } else {
+    // records in LDS: one workgroup per cloud builds the top KTD_TOP levels, then one workgroup per pending subtree
     const size_t lds = (size_t)n * 16 + (size_t)((n + 1) & ~1) * 2 + (KTB_WAVES * 6 + 8) * 4;
     if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(knn_tree_build_lds_kernel),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return PASNL_ELAUNCH;
-    const int two_phase = tune_env("PASNL_KNN_TREE_ONE_PHASE") == nullptr;  // (tuning build: A/B)
     hipLaunchKernelGGL(knn_tree_build_lds_kernel, dim3(bgrid), dim3(KTB_WAVES * 64), lds, st, b, n, support, clouds, stride, recs_off,
-                       two_phase ? KTD_TOP : 0, nflag);
-    if (two_phase) {
-      const int rc = knn_tree_deep_launch(b, n, clouds, stride, recs_off, nflag, st);
-      if (rc != PASNL_OK) return rc;
-    }
-  } else {
-    const size_t lds = (size_t)n * 8 + (size_t)((n + 1) & ~1) * 2 + (KTB_WAVES * 6 + 4) * 4;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(knn_tree_build_par_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return PASNL_ELAUNCH;
-    const int two_phase = tune_env("PASNL_KNN_TREE_ONE_PHASE") == nullptr;  // (tuning build: A/B)
-    hipLaunchKernelGGL(knn_tree_build_par_kernel, dim3(bgrid), dim3(KTB_WAVES * 64), lds, st, b, n, support, clouds, stride, recs_off,
-                       two_phase ? KTD_TOP : 0, nflag);
-    if (two_phase) {
-      const int rc = knn_tree_deep_launch(b, n, clouds, stride, recs_off, nflag, st);
-      if (rc != PASNL_OK) return rc;
-    }
+                       KTD_TOP, nflag);
   }
+  const int rc = knn_tree_deep_launch(b, n, clouds, stride, recs_off, nflag, st);
+  if (rc != PASNL_OK) return rc;
   // few queries (the flagged ones), or a shape beyond the lane-per-query kernel's packing (K > 64: a list of several registers per
   // lane; n > 65535: 16-bit arrival numbers and indices): one WAVE per query (knn_tree_search_wave_kernel)
   if (nflag || k > 64 || n > 65535) {
@@ -3460,23 +2985,12 @@ extern "C" int pasnl_knn_batch_ref(int b, int n, int m, int k, const float* supp
   hipStream_t st = pasnl_hip_stream(stream);
   char* base = static_cast<char*>(workspace);
   pasnl::KnnTieFlags flags{reinterpret_cast<int*>(base + L.nflag), reinterpret_cast<int*>(base + L.flist)};
-#ifdef PASNL_TUNING
-  const bool stamp = pasnl::tune_env("PASNL_STAMP_N") && atoi(pasnl::tune_env("PASNL_STAMP_N")) == n;
-  if (stamp) pasnl_tuning_stamp(0, st);
-#define PASNL_STAMP(i) do { if (stamp) pasnl_tuning_stamp(i, st); } while (0)
-#else
-#define PASNL_STAMP(i) do { } while (0)
-#endif
   hipLaunchKernelGGL(knn_ref_clear_kernel, dim3((b + 255) / 256), dim3(256), 0, st, b, flags.nflag, reinterpret_cast<int*>(base + L.nwork));
   int rc = pasnl::knn_grid_launch(b, n, m, k, support, queries, idx, idx_is_i64, nullptr, base + L.grid, L.tree - L.grid,
                                   max_workgroups, flags, st);
   if (rc != PASNL_OK) return rc;
-  PASNL_STAMP(1);
-  if (pasnl::tune_env("PASNL_KNN_REF_NO_TREE")) return pasnl_launch_status();  // (tuning build: the canonical search + flags alone, A/B)
-  if (const char* e = pasnl::tune_env("PASNL_KNN_REF_NO_TREE_ABOVE")) { if (n > atoi(e)) return pasnl_launch_status(); }  // (... for the large / the small
-  if (const char* e = pasnl::tune_env("PASNL_KNN_REF_NO_TREE_BELOW")) { if (n < atoi(e)) return pasnl_launch_status(); }  //      searches of a model only)
   const bool small = n <= pasnl::KTS_NMAX && k <= 64;  // one kernel: the tie paths of a cloud's few listed queries, else its tree + searches
-  if (!small && pasnl::tune_env("PASNL_KNN_REF_NO_TIE_PATH") == nullptr) {
+  if (!small) {
     // a FEW listed queries (chance ties): the runs of equal distances put in the tree's arrival order along the tree paths that
     // separate them, a workgroup per listed cloud; `nwork` (b ints behind the lists' counters) = what is left to the builds below.
     // Clouds of more than KTB_LDS_NMAX points: the form that reads the cloud in global memory (no records in LDS).
@@ -3496,12 +3010,10 @@ extern "C" int pasnl_knn_batch_ref(int b, int n, int m, int k, const float* supp
     else { if (idx_is_i64) PASNL_KTP(long long, false) else PASNL_KTP(int, false) }
 #undef PASNL_KTP
     flags.nflag = nwork;
-    if (pasnl::tune_env("PASNL_KNN_REF_TIE_PATH_ONLY")) return pasnl_launch_status();  // (tuning build: timing without the builds' launches)
   }
   if (small) {  // (tree + searches of a listed cloud in one workgroup, all in LDS)
     const size_t lds = pasnl::kts_lds_bytes(n);
-    const int grid = pasnl::tune_env("PASNL_KNN_REF_EMPTY_TREE") ? 0 : std::min(b, 64);
-    if (grid == 0) return pasnl_launch_status();
+    const int grid = std::min(b, 64);
 #define PASNL_KTS(T)                                                                                                             \
     {                                                                                                                             \
       auto kern = pasnl::knn_tree_small_kernel<T>;                                                                                \
@@ -3513,7 +3025,6 @@ extern "C" int pasnl_knn_batch_ref(int b, int n, int m, int k, const float* supp
     }
     if (idx_is_i64) PASNL_KTS(long long) else PASNL_KTS(int)
 #undef PASNL_KTS
-    PASNL_STAMP(2);
     return pasnl_launch_status();
   }
   if (n > pasnl::KTB_LDS_NMAX && n <= pasnl::KTL_NMAX && k <= 64) {
@@ -3540,23 +3051,3 @@ extern "C" int pasnl_knn_batch_ref(int b, int n, int m, int k, const float* supp
   return pasnl::knn_tree_launch(b, n, m, k, support, queries, idx, idx_is_i64, base + L.tree, L.total - L.tree, flags, depth_flag, st);
 }
 
-#ifdef PASNL_TUNING
-// time stamps inside a captured step (tools/step_stamps.py): a one-thread kernel per stamp, wall_clock64() = the 100 MHz constant clock
-__device__ unsigned long long pasnl_stamps[16];
-__global__ void pasnl_stamp_kernel(int slot) { pasnl_stamps[slot] = wall_clock64(); }
-extern "C" void pasnl_tuning_stamp(int slot, hipStream_t st) { hipLaunchKernelGGL(pasnl_stamp_kernel, dim3(1), dim3(1), 0, st, slot); }
-extern "C" int pasnl_tuning_stamps_read(unsigned long long* host16) {
-  return hipMemcpyFromSymbol(host16, HIP_SYMBOL(pasnl_stamps), sizeof(pasnl_stamps)) == hipSuccess ? 0 : -1;
-}
-extern "C" int pasnl_tie_path_wg_read(unsigned long long* host64) {
-  return hipMemcpyFromSymbol(host64, HIP_SYMBOL(pasnl::ktp_wg_cycles), sizeof(pasnl::ktp_wg_cycles)) == hipSuccess ? 0 : -1;
-}
-extern "C" int pasnl_tie_paths_read(int* host8, int clear) {
-  if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(pasnl::ktp_paths), sizeof(pasnl::ktp_paths)) != hipSuccess) return -1;
-  if (clear) { int z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(pasnl::ktp_paths), z, sizeof(z)) != hipSuccess) return -1; }
-  return 0;
-}
-extern "C" int pasnl_knn_small_probe_read(unsigned long long* host32) {
-  return hipMemcpyFromSymbol(host32, HIP_SYMBOL(pasnl::kts_probe), sizeof(pasnl::kts_probe)) == hipSuccess ? 0 : -1;
-}
-#endif

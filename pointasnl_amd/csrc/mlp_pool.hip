@@ -19,9 +19,6 @@
 // takes fewer tiles.  fp32 MFMA: an exact fmaf chain (another summation order than the vendor GEMM's: parity 1e-5 of scale).
 #include "common.hpp"
 
-#ifndef PASNL_MLP3_ABL
-#define PASNL_MLP3_ABL 0  // (diagnostic builds: 1 = no weight loads, 2 = no LDS operand reads, 4 = no tile load; results are wrong)
-#endif
 namespace pasnl {
 
 typedef float mp_f32x16 __attribute__((ext_vector_type(16)));
@@ -46,18 +43,14 @@ __device__ __forceinline__ void mp_mm(const float* xrow, int rbstride, int NBT, 
     const float* wrow = Wp + (size_t)bt * (16 * WOUT);  // (uniform: a scalar base, the lane's offset in a register)
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      if (PASNL_MLP3_ABL & 1) {
-        wa[set][i][0] = make_float4((float)bt, 1.f, 2.f, (float)loff[i]); wa[set][i][1] = wa[set][i][0];
-      } else {
-        wa[set][i][0] = *reinterpret_cast<const float4*>(wrow + loff[i]);
-        wa[set][i][1] = *reinterpret_cast<const float4*>(wrow + loff[i] + 4);
-      }
+      wa[set][i][0] = *reinterpret_cast<const float4*>(wrow + loff[i]);
+      wa[set][i][1] = *reinterpret_cast<const float4*>(wrow + loff[i] + 4);
     }
 #pragma unroll
     for (int u = 0; u < BT; ++u)
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
-        xb[set][rb][u] = (PASNL_MLP3_ABL & 2) ? (float)(bt + rb) : xrow[rb * rbstride + 2 * (bt * BT + u)];
+        xb[set][rb][u] = xrow[rb * rbstride + 2 * (bt * BT + u)];
   };
   load(0, 0);
   for (int bt = 0; bt < NBT; bt += 2) {
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(512) void mlp3_pool_kernel(int n, int k0, const flo
     for (int r = wave; r < TR; r += NW) {
       const int row = min(tile * TR + r, n - 1);
       for (int q = lane; q < q4; q += 64) {
-        const float4 v = (PASNL_MLP3_ABL & 4) ? make_float4(1.f, 2.f, 3.f, 4.f) : xc[(size_t)row * q4 + q];
+        const float4 v = xc[(size_t)row * q4 + q];
         float* d = A + r * pa + 4 * q;
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
       }

@@ -203,183 +203,6 @@ __global__ __launch_bounds__(WAVES * 64) void fps_kernel(int n, int m, const flo
   fps_emit_xyz<T>(xyz + (size_t)blockIdx.x * n * 3, picks, m, out_xyz ? out_xyz + (size_t)blockIdx.x * m * 3 : nullptr, tid);
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// Small clouds (n <= 4096, WAVES <= 4): the same algorithm with a shorter dependent chain per round.
-// What a round of fps_kernel spends after the in-lane tournament is synchronisation, not arithmetic:
-// wave max -> ballot -> readlane -> LDS slot -> barrier -> LDS read -> row DPP max -> ballot -> readlane ->
-// LDS read of the pick's coordinates.  Here the tournament carries the candidate's COORDINATES along with (d, k)
-// (a few more v_cndmask per level, off the critical path), the lane that holds the wave maximum writes
-// {d, tie key, x, y, z} to its wave's slot itself (exec-masked store: no ballot/readlane on the common path), and
-// after the ONE barrier every lane reads the WAVES slots (broadcast reads, one wait) and reduces them in registers
-// with 64-bit compares on (d bits << 32 | ~tie key): largest distance, then smallest tie key = the reference rule.
-// The winner's coordinates arrive with it: no second LDS round trip.
-// ---------------------------------------------------------------------------------------------
-template <int T, int PPL, int LO, int N>
-__device__ __forceinline__ void fps_tournament_xyz(const int (&td)[PPL], const f32x2 (&px)[PPL / 2], const f32x2 (&py)[PPL / 2],
-                                                   const f32x2 (&pz)[PPL / 2], int tid, int& d, int& k, float& x, float& y,
-                                                   float& z) {
-  if constexpr (N == 1) {
-    constexpr FpsOrder<T, PPL> ORDER{};
-    constexpr int I = ORDER.idx[LO];
-    d = td[I];
-    k = I * T + tid;
-    x = px[I / 2][I % 2];
-    y = py[I / 2][I % 2];
-    z = pz[I / 2][I % 2];
-  } else {
-    int dl, kl, dr, kr;
-    float xl, yl, zl, xr, yr, zr;
-    fps_tournament_xyz<T, PPL, LO, N / 2>(td, px, py, pz, tid, dl, kl, xl, yl, zl);
-    fps_tournament_xyz<T, PPL, LO + N / 2, N - N / 2>(td, px, py, pz, tid, dr, kr, xr, yr, zr);
-    const bool right = dr > dl;
-    d = right ? dr : dl;
-    k = right ? kr : kl;
-    x = right ? xr : xl;
-    y = right ? yr : yl;
-    z = right ? zr : zl;
-  }
-}
-
-struct __attribute__((aligned(16))) FpsSlot {
-  uint32_t nkey;  // ~tie key  (low half of the 64-bit order key)
-  int d;          // distance bits (high half)
-  float x, y;
-  float z;
-  int pad[3];
-};
-
-// best of slots [LO, LO+N): 64-bit order key (d bits << 32 | ~tie key) and the candidate's coordinates
-template <int LO, int N>
-__device__ __forceinline__ void fps_reduce_slots(const FpsSlot* slot, unsigned long long& key, float& x, float& y, float& z) {
-  if constexpr (N == 1) {
-    const float4 a = *reinterpret_cast<const float4*>(&slot[LO]);
-    key = ((unsigned long long)__float_as_uint(a.y) << 32) | __float_as_uint(a.x);
-    x = a.z;
-    y = a.w;
-    z = slot[LO].z;
-  } else {
-    unsigned long long kl, kr;
-    float xl, yl, zl, xr, yr, zr;
-    fps_reduce_slots<LO, N / 2>(slot, kl, xl, yl, zl);
-    fps_reduce_slots<LO + N / 2, N - N / 2>(slot, kr, xr, yr, zr);
-    const bool r = kr > kl;
-    key = r ? kr : kl;
-    x = r ? xr : xl;
-    y = r ? yr : yl;
-    z = r ? zr : zl;
-  }
-}
-
-#ifdef PASNL_TUNING
-#define FPS_MARK(i) do { if (dbg) { __builtin_amdgcn_sched_barrier(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-                                    __builtin_amdgcn_sched_barrier(0); acc[i] += t_ - tprev; tprev = t_; } } while (0)
-#define FPS_DBG_PARAM , long long* dbg
-#define FPS_DBG_ARG , dbg
-#else
-#define FPS_MARK(i)
-#define FPS_DBG_PARAM
-#define FPS_DBG_ARG
-#endif
-
-template <int WAVES, int PPL, int ABL = 0>  // ABL (tuning build, timing only): 1 = no cross-wave exchange, 2 = no wave reduction either
-__global__ __launch_bounds__(WAVES * 64) void fps_small_kernel(int n, int m, const float* __restrict__ xyz,
-                                                              int* __restrict__ idx FPS_DBG_PARAM) {
-  static_assert(PPL % 2 == 0 && WAVES <= 4, "");
-#ifdef PASNL_TUNING
-  unsigned long long acc[6] = {0, 0, 0, 0, 0, 0}, tprev = __builtin_amdgcn_s_memtime();
-#endif
-  constexpr int T = WAVES * 64;
-  constexpr int NP = PPL / 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  FpsSlot* slots = reinterpret_cast<FpsSlot*>(smem);                      // [2][WAVES]
-  int* picks = reinterpret_cast<int*>(smem + 2 * WAVES * sizeof(FpsSlot));  // [m]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* cloud = xyz + (size_t)blockIdx.x * n * 3;
-
-  f32x2 px[NP], py[NP], pz[NP];
-  int td[PPL];
-#pragma unroll
-  for (int q = 0; q < NP; ++q)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int k = (2 * q + e) * T + tid;
-      const bool ok = k < n;
-      px[q][e] = ok ? cloud[k * 3] : 0.f;
-      py[q][e] = ok ? cloud[k * 3 + 1] : 0.f;
-      pz[q][e] = ok ? cloud[k * 3 + 2] : 0.f;
-      td[2 * q + e] = ok ? __float_as_int(1e38f) : __float_as_int(-(float)(tid + 1));
-    }
-  float x1 = cloud[0], y1 = cloud[1], z1 = cloud[2];
-  if (tid == 0) picks[0] = 0;
-
-  for (int j = 1; j < m; ++j) {
-    FPS_MARK(0);
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      f32x2 dx = px[q] - x1, dy = py[q] - y1, dz = pz[q] - z1;
-      f32x2 d = (dx * dx + dy * dy) + dz * dz;
-      td[2 * q] = min(td[2 * q], __float_as_int(d[0]));
-      td[2 * q + 1] = min(td[2 * q + 1], __float_as_int(d[1]));
-    }
-    int bd, bk;
-    float bx, by, bz;
-    fps_tournament_xyz<T, PPL, 0, PPL>(td, px, py, pz, tid, bd, bk, bx, by, bz);
-    FPS_MARK(1);
-    if constexpr (ABL == 2) {
-      x1 = bx; y1 = by; z1 = bz;
-      if (tid == 0) picks[j] = bk;
-      continue;
-    }
-    const int wmaxi = __builtin_amdgcn_readlane(wave_max_i32_to_lane63(bd), 63);
-    FpsSlot* slot = slots + (j & 1) * WAVES;
-    const bool mine = bd == wmaxi;
-    unsigned long long tie = __ballot(mine);
-    bool writer = mine;
-    if (__builtin_popcountll(tie) > 1) writer = lane == fps_break_tie(tie, bk);  // rare, wave-uniform branch
-    if (writer) {
-      *reinterpret_cast<float4*>(&slot[wave]) =
-          make_float4(__uint_as_float(~fps_tiekey(bk)), __int_as_float(bd), bx, by);
-      slot[wave].z = bz;
-    }
-    FPS_MARK(2);
-    if constexpr (ABL == 1) {
-      x1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bx)));
-      y1 = by; z1 = bz;
-      if (tid == 0) picks[j] = bk;
-      continue;
-    }
-    if constexpr (WAVES > 1) __syncthreads();
-    else __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's own store
-    FPS_MARK(3);
-    // every lane reduces the WAVES candidates in registers (compile-time recursion: see fps_tournament)
-    unsigned long long wkey;
-    fps_reduce_slots<0, WAVES>(slot, wkey, x1, y1, z1);
-    if (tid == 0) picks[j] = (int)(~(uint32_t)wkey & 0x3fffffu);
-    FPS_MARK(4);
-  }
-#ifdef PASNL_TUNING
-  if (dbg && blockIdx.x == 0 && tid == 0)
-    for (int i = 0; i < 5; ++i) dbg[i] = (long long)acc[i];
-#endif
-  __syncthreads();
-  int* out = idx + (size_t)blockIdx.x * m;
-  for (int j = tid; j < m; j += T) out[j] = picks[j];
-}
-
-template <int WAVES, int PPL, int ABL = 0>
-static int fps_small_launch(int b, int n, int m, const float* xyz, int* idx, hipStream_t st) {
-  size_t lds = (size_t)2 * WAVES * sizeof(FpsSlot) + (size_t)m * 4;
-  if (lds > 64 * 1024) return PASNL_EUNSUPPORTED;
-#ifdef PASNL_TUNING
-  long long* dbg = nullptr;  // PASNL_FPS_PROBE=<device pointer to 8 int64, hex>: phase cycles of workgroup 0, wave 0
-  if (const char* pe = tune_env("PASNL_FPS_PROBE")) dbg = reinterpret_cast<long long*>(strtoull(pe, nullptr, 16));
-#endif
-  hipLaunchKernelGGL((fps_small_kernel<WAVES, PPL, ABL>), dim3(b), dim3(WAVES * 64), lds, st, n, m, xyz, idx FPS_DBG_ARG);
-  return pasnl_launch_status();
-}
-
 template <int WAVES, int PPL>
 static int fps_launch(int b, int n, int m, const float* xyz, int* idx, hipStream_t st, float* oxyz = nullptr) {
   size_t lds = (size_t)2 * 16 * 8 + (size_t)n * 16 + (size_t)m * 4;
@@ -418,13 +241,6 @@ __device__ __forceinline__ uint32_t fps_spread3(uint32_t v) {  // 4 bits -> ever
   return (v & 1u) | ((v & 2u) << 2) | ((v & 4u) << 4) | ((v & 8u) << 6);
 }
 
-#ifdef PASNL_TUNING
-__device__ unsigned long long fps_dbg[8];  // [active wave-rounds, wave-rounds | fps_multi, workgroup 0: touched wave-rounds, rounds, cycles: wave 1 pre-barrier, wave 0 merge, wave 1 round total, picks]
-#endif
-
-#ifndef PASNL_FPS_ABL
-#define PASNL_FPS_ABL 0  // tuning builds only: 1 = no wave is ever active (exchange cost alone), 2 = every wave always active
-#endif
 template <int WAVES, int NB>
 __global__ __launch_bounds__(WAVES * 64) void fps_pruned_kernel(int n, int m, const float* __restrict__ xyz, int* __restrict__ idx,
                                                                float* __restrict__ out_xyz) {
@@ -439,10 +255,6 @@ __global__ __launch_bounds__(WAVES * 64) void fps_pruned_kernel(int n, int m, co
   int* picks = hist + 64;                                                         // ... and [m] picks
   __shared__ float red[6][WAVES];
   __shared__ int wsum[WAVES];
-#if defined(PASNL_TUNING) && PASNL_FPS_ABL == 0
-  __shared__ int dbg_act[3][4];
-  if (threadIdx.x < 12) (&dbg_act[0][0])[threadIdx.x] = 0;
-#endif
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* cloud = xyz + (size_t)blockIdx.x * n * 3;
@@ -542,20 +354,14 @@ __global__ __launch_bounds__(WAVES * 64) void fps_pruned_kernel(int n, int m, co
   if (tid == 0) picks[0] = 0;
   float x1 = spt[0], y1 = spt[1], z1 = spt[2];
   float thr = empty_lane ? -1.f : INFINITY;  // the lane is active while dist^2(p, its box) < thr  (= its largest running distance, inflated)
-  uint32_t cand_d = PASNL_FPS_ABL == 1 ? (uint32_t)(wave + 1) : 0u, cand_k = 0u;  // the wave's candidate: largest running distance (bits), ~tie key
+  uint32_t cand_d = 0u, cand_k = 0u;  // the wave's candidate: largest running distance (bits), ~tie key
   __syncthreads();
 
   for (int j = 1; j < m; ++j) {
     const float ex = fmaxf(fmaxf(blo[0] - x1, x1 - bhi[0]), 0.f), ey = fmaxf(fmaxf(blo[1] - y1, y1 - bhi[1]), 0.f),
                 ez = fmaxf(fmaxf(blo[2] - z1, z1 - bhi[2]), 0.f);
     const float lb = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-#if defined(PASNL_TUNING) && PASNL_FPS_ABL == 0
-    if ((blockIdx.x & 3) == 0) {
-      const bool act = __ballot(lb < thr) != 0ull;
-      if (lane == 0) { atomicAdd(&fps_dbg[1], 1ull); if (act) { atomicAdd(&fps_dbg[0], 1ull); atomicAdd(&dbg_act[j % 3][wave & 3], 1); } }
-    }
-#endif
-    if ((PASNL_FPS_ABL == 2 || __ballot(lb < thr) != 0ull) && PASNL_FPS_ABL != 1) {  // wave-uniform
+    if (__ballot(lb < thr) != 0ull) {  // wave-uniform
 #pragma unroll
       for (int q = 0; q < NB / 2; ++q) {
         const f32x2 dx = px[q] - x1, dy = py[q] - y1, dz = pz[q] - z1;
@@ -602,13 +408,6 @@ __global__ __launch_bounds__(WAVES * 64) void fps_pruned_kernel(int n, int m, co
     if (lane == 0) slot[wave] = make_float2(__uint_as_float(cand_d), __uint_as_float(cand_k));
     __syncthreads();
     const float2 sv = lane < WAVES ? slot[lane] : make_float2(0.f, 0.f);
-#if defined(PASNL_TUNING) && PASNL_FPS_ABL == 0
-    if (tid == 0 && (blockIdx.x & 3) == 0) {  // rounds by the number of active waves on the busiest SIMD (waves w, w+4, .. share one)
-      const int mxa = max(max(dbg_act[j % 3][0], dbg_act[j % 3][1]), max(dbg_act[j % 3][2], dbg_act[j % 3][3]));
-      atomicAdd(&fps_dbg[2 + min(mxa, 4)], 1ull);
-      for (int q = 0; q < 4; ++q) dbg_act[(j + 2) % 3][q] = 0;
-    }
-#endif
     const int di = (int)__float_as_uint(sv.x);
     const uint32_t ki = __float_as_uint(sv.y);
     const int gmax = __builtin_amdgcn_readlane(row_max_i32_to_lane15(di), 15);
@@ -647,10 +446,6 @@ static int fps_pruned_launch(int b, int n, int m, const float* xyz, int* idx, hi
   hipLaunchKernelGGL(kern, dim3(b), dim3(WAVES * 64), lds, st, n, m, xyz, idx, oxyz);
   return pasnl_launch_status();
 }
-
-#ifdef PASNL_TUNING
-#include "../../tools/experimental/fps_multi.inc"  // several picks per round: measured slower, tuning build only (EXPERIMENTS.md)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // gather_point / grad
@@ -765,14 +560,6 @@ __global__ __launch_bounds__(256) void binary_search_kernel(int n, int m, const 
 
 using namespace pasnl;
 
-#ifdef PASNL_TUNING
-extern "C" int pasnl_fps_dbg_read(unsigned long long* host4) {
-  if (hipMemcpyFromSymbol(host4, HIP_SYMBOL(pasnl::fps_dbg), sizeof(pasnl::fps_dbg)) != hipSuccess) return -1;
-  unsigned long long zero[8] = {};
-  return hipMemcpyToSymbol(HIP_SYMBOL(pasnl::fps_dbg), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 static int fps_dispatch(int b, int n, int m, const float* xyz, int* idx, float* oxyz, pasnl_stream_t stream) {
   PASNL_REQUIRE(m > 0, PASNL_EINVAL);  // "FarthestPointSample expects positive npoint"
   PASNL_REQUIRE(b >= 0 && n > 0, PASNL_EINVAL);
@@ -780,32 +567,7 @@ static int fps_dispatch(int b, int n, int m, const float* xyz, int* idx, float* 
   if (b == 0) return PASNL_OK;
   PASNL_REQUIRE(xyz && idx, PASNL_ENULL);
   hipStream_t st = pasnl_hip_stream(stream);
-  // lanes x points-per-lane must cover n.  PASNL_FPS_CFG="waves,ppl" overrides the table (tuning only).
-  const char* cfg = tune_env("PASNL_FPS_CFG");
-  if (cfg) {
-    int w = 0, p = 0;
-    if (sscanf(cfg, "%d,%d", &w, &p) == 2 && (long)w * 64 * p >= n) {
-#define PASNL_FPS_TRY(W, P) if (w == W && p == P) return fps_launch<W, P>(b, n, m, xyz, idx, st, oxyz);
-      PASNL_FPS_TRY(1, 2) PASNL_FPS_TRY(1, 4) PASNL_FPS_TRY(1, 8) PASNL_FPS_TRY(1, 16) PASNL_FPS_TRY(2, 4) PASNL_FPS_TRY(2, 8)
-      PASNL_FPS_TRY(2, 16) PASNL_FPS_TRY(4, 2) PASNL_FPS_TRY(4, 4) PASNL_FPS_TRY(4, 8) PASNL_FPS_TRY(4, 16) PASNL_FPS_TRY(8, 2)
-      PASNL_FPS_TRY(8, 4) PASNL_FPS_TRY(8, 8) PASNL_FPS_TRY(8, 16) PASNL_FPS_TRY(16, 2) PASNL_FPS_TRY(16, 4) PASNL_FPS_TRY(16, 8)
-      PASNL_FPS_TRY(16, 10)
-#undef PASNL_FPS_TRY
-    }
-  }
-#ifdef PASNL_TUNING
-  if (cfg && cfg[0] == 'a') return fps_small_launch<4, 4, 1>(b, n, m, xyz, idx, st);
-  if (cfg && cfg[0] == 'b') return fps_small_launch<4, 4, 2>(b, n, m, xyz, idx, st);
-  if (cfg && cfg[0] == 's') {  // "s<waves>,<ppl>": the small-cloud kernel with an explicit shape
-    int w = 0, p = 0;
-    if (sscanf(cfg + 1, "%d,%d", &w, &p) == 2 && (long)w * 64 * p >= n && m <= 8192) {
-#define PASNL_FPS_TRY(W, P) if (w == W && p == P) return fps_small_launch<W, P>(b, n, m, xyz, idx, st);
-      PASNL_FPS_TRY(1, 2) PASNL_FPS_TRY(1, 4) PASNL_FPS_TRY(1, 8) PASNL_FPS_TRY(1, 16) PASNL_FPS_TRY(2, 2) PASNL_FPS_TRY(2, 4)
-      PASNL_FPS_TRY(2, 8) PASNL_FPS_TRY(2, 16) PASNL_FPS_TRY(4, 2) PASNL_FPS_TRY(4, 4) PASNL_FPS_TRY(4, 8) PASNL_FPS_TRY(4, 16)
-#undef PASNL_FPS_TRY
-    }
-  }
-#endif
+  // lanes x points-per-lane must cover n
   if (n <= 128) return fps_launch<1, 2>(b, n, m, xyz, idx, st, oxyz);
   if (n <= 256) return fps_launch<1, 4>(b, n, m, xyz, idx, st, oxyz);
   if (n <= 512) return fps_launch<1, 8>(b, n, m, xyz, idx, st, oxyz);
@@ -815,26 +577,12 @@ static int fps_dispatch(int b, int n, int m, const float* xyz, int* idx, float* 
   // 387 vs 524 at B = 2048 (tools/fps_batch_sweep.py, profiles/r04_g_fps_batch_sweep.txt)
   if (n <= 1024) return b > 640 ? fps_launch<1, 16>(b, n, m, xyz, idx, st, oxyz) : fps_launch<4, 4>(b, n, m, xyz, idx, st, oxyz);
   if (n <= 2048) return fps_launch<4, 8>(b, n, m, xyz, idx, st, oxyz);   // measured (tools/fps_cfg_sweep.py): 146 vs 207 us for (2,16) at 8x1280->320, 231 vs 329 us at 16x2048->512
-  if (!tune_env("PASNL_FPS_NOPRUNE")) {
-    // pruned rounds (fps_pruned_kernel): the unpruned kernels below stay as the A/B reference
-    int rc = PASNL_EUNSUPPORTED;
-#ifdef PASNL_TUNING
-    const char* kenv = tune_env("PASNL_FPS_K");  // 2..4 = picks per round (fps_multi_kernel, a measurement); default: one
-    const int kk = kenv ? atoi(kenv) : 0;
-#define PASNL_FPS_BIG(NB)                                                            \
-    (kk == 2 ? fps_multi_launch<16, NB, 2>(b, n, m, xyz, idx, st, oxyz)               \
-     : kk == 3 ? fps_multi_launch<16, NB, 3>(b, n, m, xyz, idx, st, oxyz)             \
-     : kk == 4 ? fps_multi_launch<16, NB, 4>(b, n, m, xyz, idx, st, oxyz)             \
-               : fps_pruned_launch<16, NB>(b, n, m, xyz, idx, st, oxyz))
-#else
-#define PASNL_FPS_BIG(NB) fps_pruned_launch<16, NB>(b, n, m, xyz, idx, st, oxyz)
-#endif
-    if (n <= 4096) rc = PASNL_FPS_BIG(4);
-    else if (n <= 8192) rc = PASNL_FPS_BIG(8);
-    else if (n <= 10240) rc = PASNL_FPS_BIG(10);
-#undef PASNL_FPS_BIG
-    if (rc != PASNL_EUNSUPPORTED) return rc;
-  }
+  // pruned rounds (fps_pruned_kernel); the unpruned kernels below take the clouds it declines (LDS too small, n > 65535)
+  int rc = PASNL_EUNSUPPORTED;
+  if (n <= 4096) rc = fps_pruned_launch<16, 4>(b, n, m, xyz, idx, st, oxyz);
+  else if (n <= 8192) rc = fps_pruned_launch<16, 8>(b, n, m, xyz, idx, st, oxyz);
+  else if (n <= 10240) rc = fps_pruned_launch<16, 10>(b, n, m, xyz, idx, st, oxyz);
+  if (rc != PASNL_EUNSUPPORTED) return rc;
   if (n <= 4096) return fps_launch<4, 16>(b, n, m, xyz, idx, st, oxyz);
   if (n <= 8192) return fps_launch<16, 8>(b, n, m, xyz, idx, st, oxyz);
   if (n <= 10240) return fps_launch<16, 10>(b, n, m, xyz, idx, st, oxyz);
@@ -846,21 +594,10 @@ extern "C" int pasnl_farthest_point_sample(int b, int n, int m, const float* xyz
   return fps_dispatch(b, n, m, xyz, idx, nullptr, stream);
 }
 
-#ifdef PASNL_TUNING
-extern "C" void pasnl_tuning_stamp(int slot, hipStream_t st);
-#endif
 extern "C" int pasnl_farthest_point_sample_gather(int b, int n, int m, const float* xyz, int* idx, float* new_xyz,
                                                   pasnl_stream_t stream) {
   PASNL_REQUIRE(b == 0 || new_xyz, PASNL_ENULL);
-#ifdef PASNL_TUNING
-  const bool stamp = pasnl::tune_env("PASNL_STAMP_N") && atoi(pasnl::tune_env("PASNL_STAMP_N")) == n;  // (tools/step_stamps.py)
-  if (stamp) pasnl_tuning_stamp(4, pasnl_hip_stream(stream));
-  const int rc = fps_dispatch(b, n, m, xyz, idx, new_xyz, stream);
-  if (stamp) pasnl_tuning_stamp(5, pasnl_hip_stream(stream));
-  return rc;
-#else
   return fps_dispatch(b, n, m, xyz, idx, new_xyz, stream);
-#endif
 }
 
 static int grid_for(long total) {

@@ -127,15 +127,18 @@ def test_variable_store_is_seeded_and_folds_bn():
 
 
 def test_product_library_reads_no_environment_variable():
-    """include/pasnl.h promises "no global state": the A/B and probe switches of the kernels (PASNL_NL_SPLIT, PASNL_BALL_PROBE
-    ...) exist only in the tuning build (-DPASNL_TUNING -> libpasnl_hip_tuning.so, which the package never loads)."""
+    """include/pasnl.h promises "no global state": the library reads no environment variable, and there is one build of it --
+    no source file holds an environment-selected switch (getenv, tune_env) or a tuning-only block, and the Makefile has no
+    tuning target."""
     import re
 
     csrc = os.path.join(ROOT, "pointasnl_amd", "csrc")
     for name in sorted(os.listdir(csrc)):
-        if not name.endswith((".hip", ".hpp")):
+        if not (name.endswith((".hip", ".hpp", ".inc", ".h")) or name == "Makefile"):
             continue
         text = open(os.path.join(csrc, name)).read()
-        text = re.sub(r"#ifdef PASNL_TUNING.*?#else", "", text, flags=re.S)
-        assert "getenv(" not in text, name
+        for word in ("getenv(", "tune_env", "PASNL_TUNING"):
+            assert word not in text, (name, word)
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert re.search(r"^[^\s#=]*tuning[^\s=]*\s*:", makefile, flags=re.M) is None
     assert "libpasnl_hip_tuning" not in open(os.path.join(ROOT, "pointasnl_amd", "_hip.py")).read()
