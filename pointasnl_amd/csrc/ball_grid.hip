@@ -663,7 +663,7 @@ int ball_grid_launch(int b, int n, int m, float radius, float thr2, int nsample,
   const size_t lds = (size_t)n * 16 + BG_WAVES * BG_REGION + (size_t)((BG_NC + 3 + 1) & ~1) * 2;
   static_assert(BG_WAVES * BG_REGION >= BG_NC * 4 + (BG_WAVES * 7 + 8) * 4, "the cell counters and the build's partials alias the wave regions");
   static_assert(1024 * 16 + BG_WAVES * BG_REGION + ((BG_NC + 3 + 1) & ~1) * 2 <= 53760, "three workgroups per CU at n <= 1024");
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
   // queries per workgroup: one round of 64 per wave; FEW clouds: a cloud's queries over four workgroups (each builds the
   // cloud's grid again, ~3 us of 8 waves, and only two of its waves walk), so that b = 64 reaches every CU: 16.9 -> 15.8 us;
   // from b = 256 on (1024 quarter chunks) it loses: 20.2 -> 28.3 us
@@ -675,20 +675,10 @@ int ball_grid_launch(int b, int n, int m, float radius, float thr2, int nsample,
   // e / d for e < 2^16 as umulhi(e, magic); d = 16-byte chunks (or entries) per row
   const unsigned div = (nsample & 3) == 0 ? (unsigned)nsample / 4 : (unsigned)nsample;
   const uint32_t ns_magic = div == 1 ? 0u : (uint32_t)((0x100000000ull / div) + 1ull);  // 0: divisor 1
-#define PASNL_BG(NW)                                                                                                     \
-  {                                                                                                                      \
-    auto gk = ball_grid_kernel<NW>;                                                                                      \
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(gk),                                        \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)      \
-      return PASNL_ELAUNCH;                                                                                              \
-    hipLaunchKernelGGL(gk, grid, dim3(BG_THREADS), lds, stream, n, m, rpad, thr2, r3, nsample, ns_magic, qchunk,          \
-                       xyz1, xyz2, idx, pts_cnt);                                                                        \
-  }
-  if (nw32 == 8) PASNL_BG(8)
-  else if (nw32 == 16) PASNL_BG(16)
-  else if (nw32 == 32) PASNL_BG(32)
-  else PASNL_BG(64)
-#undef PASNL_BG
+  auto kern = nw32 == 8 ? ball_grid_kernel<8> : nw32 == 16 ? ball_grid_kernel<16> : nw32 == 32 ? ball_grid_kernel<32> : ball_grid_kernel<64>;
+  if (launch(kern, grid, dim3(BG_THREADS), lds, stream, n, m, rpad, thr2, r3, nsample, ns_magic, qchunk, xyz1, xyz2, idx,
+             pts_cnt) != PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 

@@ -1671,30 +1671,27 @@ static int nl_mfma_launch(int b, int p, int n, float qscale, const float* q, con
   if constexpr (CB <= 64) {
     if (!staged) {  // (the LDS-staged kernel stays selectable -- variant 3 -- for A/B measurements)
       const size_t lds = (size_t)SPLIT * (CB / 2 + 2) * 64 * sizeof(float);
-      hipLaunchKernelGGL((nl_attention_direct_kernel<CB, SPLIT>), dim3((p + 31) / 32, b), dim3(SPLIT * 64), lds, st, p, n, qscale,
-                         q, kv, out);
+      if (launch(nl_attention_direct_kernel<CB, SPLIT>, dim3((p + 31) / 32, b), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv,
+                 out) != PASNL_OK)
+        return PASNL_ELAUNCH;
       return pasnl_launch_status();
     }
   }
   constexpr int WAVE_FLOATS = NL_KB * (CB + 1) + NL_KB * CB + 3;
   size_t lds = (size_t)SPLIT * ((WAVE_FLOATS + 3) & ~3) * 4 + 16;
-  auto kern = nl_attention_mfma_kernel<CB, SPLIT>;
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
+  if (launch(nl_attention_mfma_kernel<CB, SPLIT>, dim3((p + 31) / 32, b), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv, out) !=
+      PASNL_OK)
     return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((p + 31) / 32, b), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv, out);
   return pasnl_launch_status();
 }
 
 template <int SPLIT>
 static int nl_pair_launch(int b, int p, int n, float qscale, const float* q, const float* kv, float* out, hipStream_t st) {
   const size_t lds = (size_t)SPLIT * 2 * (32 / 2 + 2) * 64 * sizeof(float);
-  auto kern = nl_attention_pair_kernel<SPLIT>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (launch(nl_attention_pair_kernel<SPLIT>, dim3((p + 63) / 64, b), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv, out, 0,
+             static_cast<float*>(nullptr)) != PASNL_OK)
     return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((p + 63) / 64, b), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv, out, 0, static_cast<float*>(nullptr));
   return pasnl_launch_status();
 }
 
@@ -1725,12 +1722,10 @@ template <int SPLIT>
 static int nl_pair_parts_launch(int b, int p, int n, float qscale, const float* q, const float* kv, float* out, int kparts, float* part,
                                 hipStream_t st) {
   const size_t lds = (size_t)SPLIT * 2 * (32 / 2 + 2) * 64 * sizeof(float);
-  auto kern = nl_attention_pair_kernel<SPLIT, true>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
   const int blocks = n / NL_KB, bpz = (blocks + kparts - 1) / kparts;
-  hipLaunchKernelGGL(kern, dim3((p + 63) / 64, b, kparts), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv, out, bpz, part);
+  if (launch(nl_attention_pair_kernel<SPLIT, true>, dim3((p + 63) / 64, b, kparts), dim3(SPLIT * 64), lds, st, p, n, qscale, q, kv,
+             out, bpz, part) != PASNL_OK)
+    return PASNL_ELAUNCH;
   hipLaunchKernelGGL(nl_attention_merge_kernel, dim3((p + 63) / 64, b), dim3(64), 0, st, p, kparts, part, out);
   return pasnl_launch_status();
 }
@@ -2294,27 +2289,13 @@ extern "C" int pasnl_as_cell_wide_ld(int g, int as, int cb, int w, int ch, const
   const long cap = 768;  // persistent workgroups: a wave's weights (registers) and the workgroup's Wb (LDS) are loaded once
   const dim3 grid((unsigned)(wgs < cap ? wgs : cap)), block(256);
   hipStream_t st = pasnl_hip_stream(stream);
-#define PASNL_AS_GO(CBLK)                                                                                                  \
-  do {                                                                                                                     \
-    auto kern = pasnl::as_cell_wide_kernel<CBLK>;                                                                          \
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                               (int)lds) != hipSuccess)                                                    \
-      return PASNL_ELAUNCH;                                                                                                \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, (long)g, as, cb, w, ch, qscale, kvq, ld, x, wa, ba, wb, bb, new_xyz,    \
-                       new_feature);                                                                                       \
-  } while (0)
-  switch ((cb + 15) / 16) {  // exact: the kernel treats every block of 16 channels but the last as full
-    case 1: PASNL_AS_GO(1); break;
-    case 2: PASNL_AS_GO(2); break;
-    case 3: PASNL_AS_GO(3); break;
-    case 4: PASNL_AS_GO(4); break;
-    case 5: PASNL_AS_GO(5); break;
-    case 6: PASNL_AS_GO(6); break;
-    case 7: PASNL_AS_GO(7); break;
-    case 8: PASNL_AS_GO(8); break;
-    default: PASNL_AS_GO(9); break;
-  }
-#undef PASNL_AS_GO
+  static const decltype(&as_cell_wide_kernel<1>) kernels[] = {as_cell_wide_kernel<1>, as_cell_wide_kernel<2>, as_cell_wide_kernel<3>,
+                                                               as_cell_wide_kernel<4>, as_cell_wide_kernel<5>, as_cell_wide_kernel<6>,
+                                                               as_cell_wide_kernel<7>, as_cell_wide_kernel<8>, as_cell_wide_kernel<9>};
+  const int cblk = (cb + 15) / 16;  // exact: the kernel treats every block of 16 channels but the last as full
+  if (launch(kernels[(cblk < 9 ? cblk : 9) - 1], grid, block, lds, st, (long)g, as, cb, w, ch, qscale, kvq, ld, x, wa, ba, wb, bb,
+             new_xyz, new_feature) != PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 
@@ -2337,12 +2318,9 @@ extern "C" int pasnl_as_cell_narrow(int g, int as, int cb, int w, int ch, const 
   const dim3 grid((unsigned)(wgs < 2048 ? wgs : 2048)), block(256);
   hipStream_t st = pasnl_hip_stream(stream);
   const int ks = (w + 1 + 3) / 4;
-#define PASNL_AS_GO(KS, CBLK)                                                                                            \
-  hipLaunchKernelGGL((pasnl::as_cell_narrow_kernel<KS, CBLK>), grid, block, 0, st, (long)g, as, w, ch, qscale, x, wkvq, bkvq, wa, \
-                     ba, wb, bb, new_xyz, new_feature)
-  if (cb == 32) { if (ks <= 2) PASNL_AS_GO(2, 2); else if (ks == 3) PASNL_AS_GO(3, 2); else PASNL_AS_GO(4, 2); }
-  else { if (ks <= 2) PASNL_AS_GO(2, 4); else if (ks == 3) PASNL_AS_GO(3, 4); else PASNL_AS_GO(4, 4); }
-#undef PASNL_AS_GO
+  auto kern = cb == 32 ? (ks <= 2 ? as_cell_narrow_kernel<2, 2> : ks == 3 ? as_cell_narrow_kernel<3, 2> : as_cell_narrow_kernel<4, 2>)
+                       : (ks <= 2 ? as_cell_narrow_kernel<2, 4> : ks == 3 ? as_cell_narrow_kernel<3, 4> : as_cell_narrow_kernel<4, 4>);
+  hipLaunchKernelGGL(kern, grid, block, 0, st, (long)g, as, w, ch, qscale, x, wkvq, bkvq, wa, ba, wb, bb, new_xyz, new_feature);
   return pasnl_launch_status();
 }
 
@@ -2358,11 +2336,9 @@ extern "C" int pasnl_as_attention_proj(int g, int as, int cb, int w, const float
   const dim3 grid((unsigned)(wgs < 2048 ? wgs : 2048)), block(256);  // persistent: a lane's weights are loaded once
   hipStream_t st = pasnl_hip_stream(stream);
   const int ks = (w + 1 + 3) / 4;
-#define PASNL_AS_GO(KS, CBLK) \
-  hipLaunchKernelGGL((pasnl::as_attention_proj_kernel<KS, CBLK>), grid, block, 0, st, (long)g, as, w, qscale, x, wkvq, bkvq, out)
-  if (cb == 32) { if (ks <= 2) PASNL_AS_GO(2, 2); else if (ks == 3) PASNL_AS_GO(3, 2); else PASNL_AS_GO(4, 2); }
-  else { if (ks <= 2) PASNL_AS_GO(2, 4); else if (ks == 3) PASNL_AS_GO(3, 4); else PASNL_AS_GO(4, 4); }
-#undef PASNL_AS_GO
+  auto kern = cb == 32 ? (ks <= 2 ? as_attention_proj_kernel<2, 2> : ks == 3 ? as_attention_proj_kernel<3, 2> : as_attention_proj_kernel<4, 2>)
+                       : (ks <= 2 ? as_attention_proj_kernel<2, 4> : ks == 3 ? as_attention_proj_kernel<3, 4> : as_attention_proj_kernel<4, 4>);
+  hipLaunchKernelGGL(kern, grid, block, 0, st, (long)g, as, w, qscale, x, wkvq, bkvq, out);
   return pasnl_launch_status();
 }
 
@@ -2440,17 +2416,14 @@ static int local_cell_launch(long groups, int k, int w, const float* x, const fl
                              const float* w1, const float* b1, const float* ww, const float* bw, float* out, hipStream_t st) {
   const int wp = (w + 31) & ~31;
   size_t lds = ((size_t)wp * C1 + (size_t)C1 * C2 + 4 * 32 + C1) * sizeof(float);
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
-  auto kern = sa_local_cell_kernel<C1, C2>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
   // persistent workgroups: the weights are staged into LDS once per workgroup
   long wgs = (groups + 3) / 4;
   int per_cu = lds > 80 * 1024 ? 1 : (lds > 40 * 1024 ? 2 : 3);
   long cap = 256L * per_cu;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(256), lds, st, groups, k, w, x, w0, b0, w1, b1,
-                     ww, bw, out);
+  if (launch(sa_local_cell_kernel<C1, C2>, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(256), lds, st, groups, k, w, x, w0, b0, w1,
+             b1, ww, bw, out) != PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 
@@ -2468,11 +2441,8 @@ static int sa_cell_launch(long groups, int k, int w, SaGatherSrc src, const floa
                           const float* b1, const float* ww, const float* bw, float* out, hipStream_t st) {
   const int wp = (8 + (w - 6) + 31) & ~31;  // internal width: [xyz-c | xyz | 1 | 0 | feature], padded to 32-chunks
   size_t lds = ((PRE ? 0 : (size_t)wp * C1) + (size_t)C1 * C2 + 6 * 32 + (size_t)NW * SA_SKIP_REP * (wp + 4)) * sizeof(float);
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
   auto kern = sa_cell_kernel<C1, C2, NW, VEC, TAIL8, XYZ3, SINGLE, PRE>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
   // persistent workgroups (the weights are staged into LDS once per workgroup): exactly as many as are resident at once
   long wgs = (groups + NW - 1) / NW;
   int per_cu = 0;
@@ -2483,8 +2453,9 @@ static int sa_cell_launch(long groups, int k, int w, SaGatherSrc src, const floa
   // kernels keep some CUs busy) was measured and lost (cls layer2: 429 / 455 / 505 / 528 us at 1x / 2x / 4x / 8x, and
   // the two-lane cls step 1.52 / 1.54 / 1.60 / 1.65 ms).
   long cap = 256L * per_cu;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(NW * 64), lds, st, groups, k, w, src, w0, b0, w1, b1, ww,
-                     bw, out);
+  if (launch(kern, dim3((unsigned)(wgs < cap ? wgs : cap)), dim3(NW * 64), lds, st, groups, k, w, src, w0, b0, w1, b1, ww, bw, out) !=
+      PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 
@@ -2812,14 +2783,12 @@ static int sa_cell_wide_launch(long groups, int w, SaGatherSrc src, const float*
                                const float* w0p = nullptr, const float* w1p = nullptr) {
   const int wi = 8 + (w - 6);
   const size_t lds = ((size_t)32 * (wi + 1) + (CONV1 ? (size_t)32 * (C + 1) : 0) + 32) * sizeof(float);
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
   // packed operands: both matrices (the one convolution a layer has, when it has one), 16-byte aligned
   const bool packed = w0p && (!CONV1 || w1p) && (reinterpret_cast<uintptr_t>(w0p) | reinterpret_cast<uintptr_t>(w1p)) % 16 == 0;
   auto kern = packed ? sa_cell_wide_kernel<C, CONV1, true> : sa_cell_wide_kernel<C, CONV1, false>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (launch(kern, dim3((unsigned)groups), dim3(C / 32 * 64), lds, st, w, src, w0, b0, w1, b1, ww, bw, out, w0p, w1p) != PASNL_OK)
     return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(C / 32 * 64), lds, st, w, src, w0, b0, w1, b1, ww, bw, out, w0p, w1p);
   return pasnl_launch_status();
 }
 
@@ -3044,13 +3013,11 @@ static int sa_project_launch(int rows, int cf, const float* xyz, const float* fe
                              float* proj, hipStream_t st) {
   const int wp = (8 + cf + 31) & ~31;
   const size_t lds = (size_t)wp * C1 * sizeof(float);
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
-  auto kern = sa_project_kernel<C1>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
   const long tiles = (rows + 31) / 32;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((tiles + 3) / 4)), dim3(256), lds, st, rows, cf, xyz, feature, w0, b0, proj);
+  if (launch(sa_project_kernel<C1>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), lds, st, rows, cf, xyz, feature, w0, b0, proj) !=
+      PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 
@@ -3345,18 +3312,16 @@ static int sa_tail_entry(int rows, int w, int cb, int c, const float* after, con
   PASNL_REQUIRE(after && skip_max && ws && bs && wagg && bagg && out, PASNL_ENULL);
   PASNL_REQUIRE(cb == 0 || (att && wb && bb), PASNL_ENULL);
   const size_t lds = ((size_t)c + ((w + 31) & ~31) + ((cb + 31) & ~31)) * 33 * sizeof(float);  // tiles padded to 2 TAIL_KS rows
-  PASNL_REQUIRE(lds <= 160 * 1024, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(lds <= pasnl::LDS_MAX_BYTES, PASNL_EUNSUPPORTED);
   const int nw = c <= 128 ? 4 : (c <= 256 ? 8 : 16);  // one wave per 32-channel block (>= 4 waves stage the tiles)
   if (packed)
     PASNL_REQUIRE((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(wagg) | (cb ? reinterpret_cast<uintptr_t>(wb) : 0)) % 16 == 0,
                   PASNL_EUNSUPPORTED);
   auto kern = packed ? (nw == 4 ? pasnl::sa_tail_kernel<4, true> : (nw == 8 ? pasnl::sa_tail_kernel<8, true> : pasnl::sa_tail_kernel<16, true>))
                      : (nw == 4 ? pasnl::sa_tail_kernel<4, false> : (nw == 8 ? pasnl::sa_tail_kernel<8, false> : pasnl::sa_tail_kernel<16, false>));
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (pasnl::launch(kern, dim3((unsigned)((rows + 31) / 32)), dim3(nw * 64), lds, pasnl_hip_stream(stream), (long)rows, w, cb, c,
+                    after, skip_max, cb ? att : nullptr, ws, bs, wb, bb, wagg, bagg, out, xyz3, out_cat, residual) != PASNL_OK)
     return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 31) / 32)), dim3(nw * 64), lds, pasnl_hip_stream(stream), (long)rows, w, cb, c,
-                     after, skip_max, cb ? att : nullptr, ws, bs, wb, bb, wagg, bagg, out, xyz3, out_cat, residual);
   return pasnl_launch_status();
 }
 
@@ -3547,10 +3512,9 @@ extern "C" int pasnl_decode_cell_tiled(int b, int n, int c, int k, const float* 
   const bool v4 = c % 128 == 0 && reinterpret_cast<uintptr_t>(feature) % 16 == 0;
   hipStream_t st = pasnl_hip_stream(stream);
   const bool nt = (size_t)n * c * sizeof(float) >= (1u << 20);  // a cloud's feature table is worth protecting in L2
-  const void* kern = nullptr;
-#define PASNL_DT(V, NT) reinterpret_cast<const void*>(pasnl::decode_cell_tiled_kernel<16, V, NT>)
-  kern = v4 ? (nt ? PASNL_DT(4, true) : PASNL_DT(4, false)) : (nt ? PASNL_DT(1, true) : PASNL_DT(1, false));
-#undef PASNL_DT
+  auto tiled = v4 ? (nt ? pasnl::decode_cell_tiled_kernel<16, 4, true> : pasnl::decode_cell_tiled_kernel<16, 4, false>)
+                  : (nt ? pasnl::decode_cell_tiled_kernel<16, 1, true> : pasnl::decode_cell_tiled_kernel<16, 1, false>);
+  const void* kern = reinterpret_cast<const void*>(tiled);
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
   long wgs = (points + 3) / 4;

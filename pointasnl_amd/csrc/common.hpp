@@ -212,6 +212,31 @@ __device__ __forceinline__ void knn_flag_query(const KnnTieFlags f, int bi, int 
 // The library reads no environment variable and keeps no global state (include/pasnl.h), so a launch is a pure function
 // of its arguments.
 
+// ---- host side: launches
+// Dynamic LDS per workgroup: up to LDS_DEFAULT_BYTES a kernel launches as it is; beyond that, up to gfx950's LDS_MAX_BYTES,
+// HIP wants the kernel opted in first.
+constexpr size_t LDS_DEFAULT_BYTES = 48 * 1024;
+constexpr size_t LDS_MAX_BYTES = 160 * 1024;
+
+// kernel<<<grid, block, lds_bytes, stream>>>(args...), the kernel opted in to lds_bytes first where they exceed the default.
+// PASNL_ELAUNCH if the opt-in fails (nothing is launched), else PASNL_OK: the launch's own status is the caller's
+// pasnl_launch_status(), once after all of its launches.
+template <class... Params, class... Args>
+int launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args... args) {
+  if (lds_bytes > LDS_DEFAULT_BYTES && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+    return PASNL_ELAUNCH;
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+  return PASNL_OK;
+}
+
+// f(tag) with a long long tag if idx_is_i64, else an int tag: the kNN entries' index type is decltype(tag).
+template <class F>
+decltype(auto) with_index_type(int idx_is_i64, F&& f) {
+  if (idx_is_i64) return f((long long)0);
+  return f(0);
+}
+
 // internal launchers behind pasnl_knn_batch / _ws / _tree / _ref (host side; defined in grouping.hip, knn_grid.hip, knn_tree.hip)
 int knn_brute_launch(int b, int n, int m, int k, const float* support, const float* queries, void* idx, int idx_is_i64, float* dist2,
                      KnnTieFlags flags, hipStream_t st);

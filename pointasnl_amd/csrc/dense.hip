@@ -230,22 +230,9 @@ extern "C" int pasnl_dense_rows(int rows, int kdim, int n, const float* x, const
   hipStream_t st = pasnl_hip_stream(stream);
   const dim3 grid(p.ncb, p.ksplit);
   const size_t lds = (size_t)4 * p.rb * 1024 * 4;
-#define PASNL_DENSE(RB)                                                                                                   \
-  {                                                                                                                        \
-    auto kern = dense_rows_kernel<RB>;                                                                                     \
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                (int)lds) != hipSuccess)                                                  \
-      return PASNL_ELAUNCH;                                                                                                \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, rows, kdim, n, p.kchunk, p.ksplit, x, w, bias, relu, out, part,     \
-                       counters);                                                                                          \
-  }
-  switch (p.rb) {
-    case 1: PASNL_DENSE(1) break;
-    case 2: PASNL_DENSE(2) break;
-    case 3: PASNL_DENSE(3) break;
-    default: PASNL_DENSE(4) break;
-  }
-#undef PASNL_DENSE
+  auto kern = p.rb == 1 ? dense_rows_kernel<1> : p.rb == 2 ? dense_rows_kernel<2> : p.rb == 3 ? dense_rows_kernel<3> : dense_rows_kernel<4>;
+  if (launch(kern, grid, dim3(256), lds, st, rows, kdim, n, p.kchunk, p.ksplit, x, w, bias, relu, out, part, counters) != PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 

@@ -777,14 +777,11 @@ extern "C" int pasnl_query_ball_point(int b, int n, int m, float radius, int nsa
   const int rc = ball_grid_launch(b, n, m, radius, thr2, nsample, xyz1, xyz2, idx, pts_cnt, pasnl_hip_stream(stream));
   if (rc != PASNL_EUNSUPPORTED) return rc;
   size_t lds = (size_t)SEARCH_TILE * 12 + (size_t)SEARCH_WAVES * QW * nsample * sizeof(int);
-  PASNL_REQUIRE(lds <= 160 * 1024, PASNL_EUNSUPPORTED);
-  auto kern = ball_query_kernel<QW>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
+  PASNL_REQUIRE(lds <= LDS_MAX_BYTES, PASNL_EUNSUPPORTED);
   int qpb = SEARCH_WAVES * QW;
-  hipLaunchKernelGGL(kern, dim3((m + qpb - 1) / qpb, b), dim3(SEARCH_WAVES * 64), lds, pasnl_hip_stream(stream), n, m, thr2,
-                     nsample, xyz1, xyz2, idx, pts_cnt);
+  if (launch(ball_query_kernel<QW>, dim3((m + qpb - 1) / qpb, b), dim3(SEARCH_WAVES * 64), lds, pasnl_hip_stream(stream), n, m, thr2,
+             nsample, xyz1, xyz2, idx, pts_cnt) != PASNL_OK)
+    return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 
@@ -793,12 +790,10 @@ static int knn_launch(int b, int n, int m, int k, const float* support, const fl
                       float* dist2, pasnl::KnnTieFlags flags, hipStream_t st) {
   int qpb = SEARCH_WAVES * QW;
   dim3 grid((m + qpb - 1) / qpb, b), block(SEARCH_WAVES * 64);
-  if (idx_is_i64)
-    hipLaunchKernelGGL((knn_kernel<SLOTS, QW, long long>), grid, block, 0, st, n, m, k, support, queries,
-                       static_cast<long long*>(idx), dist2, flags);
-  else
-    hipLaunchKernelGGL((knn_kernel<SLOTS, QW, int>), grid, block, 0, st, n, m, k, support, queries, static_cast<int*>(idx),
-                       dist2, flags);
+  with_index_type(idx_is_i64, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((knn_kernel<SLOTS, QW, T>), grid, block, 0, st, n, m, k, support, queries, static_cast<T*>(idx), dist2, flags);
+  });
   return pasnl_launch_status();
 }
 
@@ -827,12 +822,12 @@ int pasnl::knn_brute_launch(int b, int n, int m, int k, const float* support, co
     constexpr long min_waves = 8192;
     const int qw = nq >= 4L * min_waves ? 4 : (nq >= 2L * min_waves ? 2 : 1);
     dim3 grid((m + SEARCH_WAVES * qw - 1) / (SEARCH_WAVES * qw), b), block(SEARCH_WAVES * 64);
-#define PASNL_KNN2Q(RR, Q, T) hipLaunchKernelGGL((knn2_kernel<RR, Q, T>), grid, block, 0, st, n, m, k, support, queries, static_cast<T*>(idx), dist2, flags)
-#define PASNL_KNN2(RR, T) { if (qw == 4) PASNL_KNN2Q(RR, 4, T); else if (qw == 2) PASNL_KNN2Q(RR, 2, T); else PASNL_KNN2Q(RR, 1, T); }
-    if (k <= 32) { if (idx_is_i64) PASNL_KNN2(1, long long) else PASNL_KNN2(1, int) }
-    else { if (idx_is_i64) PASNL_KNN2(2, long long) else PASNL_KNN2(2, int) }
-#undef PASNL_KNN2Q
-#undef PASNL_KNN2
+    with_index_type(idx_is_i64, [&](auto tag) {
+      using T = decltype(tag);
+      auto kern = k <= 32 ? (qw == 4 ? knn2_kernel<1, 4, T> : qw == 2 ? knn2_kernel<1, 2, T> : knn2_kernel<1, 1, T>)
+                          : (qw == 4 ? knn2_kernel<2, 4, T> : qw == 2 ? knn2_kernel<2, 2, T> : knn2_kernel<2, 1, T>);
+      hipLaunchKernelGGL(kern, grid, block, 0, st, n, m, k, support, queries, static_cast<T*>(idx), dist2, flags);
+    });
     return pasnl_launch_status();
   }
   if (k <= 64) return knn_launch<1, 4>(b, n, m, k, support, queries, idx, idx_is_i64, dist2, flags, st);
@@ -872,12 +867,14 @@ extern "C" int pasnl_sa_group(int b, int n, int c, int m, int k, const float* xy
   hipStream_t st = pasnl_hip_stream(stream);
   if (W <= 256) {
     size_t lds = (size_t)k * 4 + (size_t)(256 / W) * W * 4;
-    hipLaunchKernelGGL(sa_group_kernel<256>, dim3((unsigned)groups), dim3(256), lds, st, n, c, m, k, xyz, feature, idx, new_xyz,
-                       new_point, skip_max);
+    if (launch(sa_group_kernel<256>, dim3((unsigned)groups), dim3(256), lds, st, n, c, m, k, xyz, feature, idx, new_xyz, new_point,
+               skip_max) != PASNL_OK)
+      return PASNL_ELAUNCH;
   } else {
     size_t lds = (size_t)k * 4 + (size_t)(W <= 512 ? (512 / W) * W : 0) * 4;
-    hipLaunchKernelGGL(sa_group_kernel<512>, dim3((unsigned)groups), dim3(512), lds, st, n, c, m, k, xyz, feature, idx, new_xyz,
-                       new_point, skip_max);
+    if (launch(sa_group_kernel<512>, dim3((unsigned)groups), dim3(512), lds, st, n, c, m, k, xyz, feature, idx, new_xyz, new_point,
+               skip_max) != PASNL_OK)
+      return PASNL_ELAUNCH;
   }
   return pasnl_launch_status();
 }
@@ -918,10 +915,7 @@ static int grad_det(int b, int n, int c, long entries, int rep, const float* src
   int* start = static_cast<int*>(ws);
   int* list = start + (size_t)b * (n + 1);
   size_t lds = (size_t)n * sizeof(int);
-  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(grad_lists_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(grad_lists_kernel, dim3(b), dim3(GL_THREADS), lds, st, n, entries, idx, start, list);
+  if (launch(grad_lists_kernel, dim3(b), dim3(GL_THREADS), lds, st, n, entries, idx, start, list) != PASNL_OK) return PASNL_ELAUNCH;
   long rows = (long)b * n;
   hipLaunchKernelGGL(grad_segsum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, n, c, entries, rep, src, weight, start,
                      list, dst, rows);

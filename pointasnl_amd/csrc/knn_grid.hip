@@ -575,17 +575,14 @@ int pasnl::knn_grid_launch(int b, int n, int m, int k, const float* support, con
   dim3 grid((m + KG_WAVES - 1) / KG_WAVES, b), block(KG_WAVES * 64);
   const bool bg = max_workgroups > 0;  // the background form: a capped grid that loops
   if (bg) grid.x = (unsigned)std::max(1, std::min((int)grid.x, max_workgroups / b));
-#define PASNL_KG(RR, WW, T)                                                                                                   \
-  {                                                                                                                            \
-    if (bg) hipLaunchKernelGGL((knn_grid_query_kernel<RR, WW, T, true>), grid, block, 0, st, n, m, k, queries,                 \
-                               static_cast<const char*>(workspace), stride, static_cast<T*>(idx), dist2, flags);               \
-    else hipLaunchKernelGGL((knn_grid_query_kernel<RR, WW, T, false>), grid, block, 0, st, n, m, k, queries,                   \
-                            static_cast<const char*>(workspace), stride, static_cast<T*>(idx), dist2, flags);                  \
-  }
-  if (k <= 16) { if (idx_is_i64) PASNL_KG(1, false, long long) else PASNL_KG(1, false, int) }
-  else if (k <= 32) { if (idx_is_i64) PASNL_KG(1, true, long long) else PASNL_KG(1, true, int) }
-  else { if (idx_is_i64) PASNL_KG(2, true, long long) else PASNL_KG(2, true, int) }
-#undef PASNL_KG
+  with_index_type(idx_is_i64, [&](auto tag) {
+    using T = decltype(tag);
+    auto kern = k <= 16   ? (bg ? knn_grid_query_kernel<1, false, T, true> : knn_grid_query_kernel<1, false, T, false>)
+                : k <= 32 ? (bg ? knn_grid_query_kernel<1, true, T, true> : knn_grid_query_kernel<1, true, T, false>)
+                          : (bg ? knn_grid_query_kernel<2, true, T, true> : knn_grid_query_kernel<2, true, T, false>);
+    hipLaunchKernelGGL(kern, grid, block, 0, st, n, m, k, queries, static_cast<const char*>(workspace), stride, static_cast<T*>(idx),
+                       dist2, flags);
+  });
   return pasnl_launch_status();
 }
 
@@ -611,9 +608,8 @@ extern "C" int pasnl_knn_distance_pick(int b, int n, int nq, int k, const float*
   if (b == 0 || nq == 0) return PASNL_OK;
   PASNL_REQUIRE(pts && rnd && idx && queries, PASNL_ENULL);
   const size_t lds = (size_t)n * sizeof(int);
-  if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(knn_distance_pick_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (launch(knn_distance_pick_kernel, dim3(b), dim3(KD_T), lds, pasnl_hip_stream(stream), n, nq, k, pts, rnd, idx, queries) !=
+      PASNL_OK)
     return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(knn_distance_pick_kernel, dim3(b), dim3(KD_T), lds, pasnl_hip_stream(stream), n, nq, k, pts, rnd, idx, queries);
   return pasnl_launch_status();
 }

@@ -2105,7 +2105,7 @@ __host__ __device__ constexpr size_t kts_lds_bytes(int n) {
   return (size_t)n * 16 + (((size_t)n * 2 + 15) & ~(size_t)15) + (size_t)KTS_NNODES(n) * sizeof(KtNode) + 2 * lq * sizeof(KtWork) + 64 +
          KTB_WAVES * 6 * 4 + (size_t)KTB_WAVES * KT_DEPTH * 3 * 4 + KTS_RED_WORDS * 4 + ((sizeof(KtpShared) + 15) & ~(size_t)15);
 }
-static_assert(kts_lds_bytes(KTS_NMAX) <= 160 * 1024 && ktp_lds_bytes(KTB_LDS_NMAX) <= 160 * 1024, "a workgroup's LDS");
+static_assert(kts_lds_bytes(KTS_NMAX) <= LDS_MAX_BYTES && ktp_lds_bytes(KTB_LDS_NMAX) <= LDS_MAX_BYTES, "a workgroup's LDS");
 template <typename IdxT>
 __global__ __launch_bounds__(KTB_WAVES * 64) void knn_tree_small_kernel(int b, int n, int m, int k, const float* __restrict__ pts_all,
                                                                        const float* __restrict__ queries, IdxT* __restrict__ out,
@@ -2841,12 +2841,8 @@ static int knn_tree_deep_launch(int b, int n, char* clouds, size_t stride, size_
   const size_t with_q = ((c * 18 + 15) & ~(size_t)15) + fixed + 2 * (c / (KT_LEAF + 1) + 2) * sizeof(KtWork);
   const size_t without = ((cmax * 18 + 15) & ~(size_t)15) + fixed;
   const size_t lds2 = with_q > without ? with_q : without;
-  if (lds2 > 160 * 1024) return PASNL_EUNSUPPORTED;
-  if (lds2 > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(knn_tree_build_deep_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-    return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(knn_tree_build_deep_kernel, dim3(grid), dim3(KTB_WAVES * 64), lds2, st, b, n, clouds, stride, recs_off, nflag);
-  return PASNL_OK;
+  if (lds2 > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
+  return launch(knn_tree_build_deep_kernel, dim3(grid), dim3(KTB_WAVES * 64), lds2, st, b, n, clouds, stride, recs_off, nflag);
 }
 
 // The workspace's first 256 bytes (the flag word and its padding) zeroed by a KERNEL: a hipMemsetAsync of them captured into a
@@ -2892,42 +2888,36 @@ int pasnl::knn_tree_launch(int b, int n, int m, int k, const float* support, con
   } else {
     // records in LDS: one workgroup per cloud builds the top KTD_TOP levels, then one workgroup per pending subtree
     const size_t lds = (size_t)n * 16 + (size_t)((n + 1) & ~1) * 2 + (KTB_WAVES * 6 + 8) * 4;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(knn_tree_build_lds_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (launch(knn_tree_build_lds_kernel, dim3(bgrid), dim3(KTB_WAVES * 64), lds, st, b, n, support, clouds, stride, recs_off, KTD_TOP,
+               nflag) != PASNL_OK)
       return PASNL_ELAUNCH;
-    hipLaunchKernelGGL(knn_tree_build_lds_kernel, dim3(bgrid), dim3(KTB_WAVES * 64), lds, st, b, n, support, clouds, stride, recs_off,
-                       KTD_TOP, nflag);
   }
-  const int rc = knn_tree_deep_launch(b, n, clouds, stride, recs_off, nflag, st);
+  int rc = knn_tree_deep_launch(b, n, clouds, stride, recs_off, nflag, st);
   if (rc != PASNL_OK) return rc;
   // few queries (the flagged ones), or a shape beyond the lane-per-query kernel's packing (K > 64: a list of several registers per
   // lane; n > 65535: 16-bit arrival numbers and indices): one WAVE per query (knn_tree_search_wave_kernel)
   if (nflag || k > 64 || n > 65535) {
     const long waves = nflag ? 1024L : (long)b * m;
     const dim3 wgrid((unsigned)std::min((waves + KTW_WAVES - 1) / KTW_WAVES, 16384L));
-#define PASNL_KT_WAVE(T, S)                                                                                                       \
-    hipLaunchKernelGGL((knn_tree_search_wave_kernel<T, S>), wgrid, dim3(KTW_WAVES * 64), 0, st, b, n, m, k, queries, clouds, stride, \
-                       recs_off, static_cast<T*>(idx), flag, nflag, only.flist)
-#define PASNL_KT_WAVES(S) { if (idx_is_i64) PASNL_KT_WAVE(long long, S); else PASNL_KT_WAVE(int, S); }
-    if (k <= 64) PASNL_KT_WAVES(1) else if (k <= 128) PASNL_KT_WAVES(2) else PASNL_KT_WAVES(4)
-#undef PASNL_KT_WAVES
-#undef PASNL_KT_WAVE
+    with_index_type(idx_is_i64, [&](auto tag) {
+      using T = decltype(tag);
+      auto kern = k <= 64    ? knn_tree_search_wave_kernel<T, 1>
+                  : k <= 128 ? knn_tree_search_wave_kernel<T, 2>
+                             : knn_tree_search_wave_kernel<T, 4>;
+      hipLaunchKernelGGL(kern, wgrid, dim3(KTW_WAVES * 64), 0, st, b, n, m, k, queries, clouds, stride, recs_off, static_cast<T*>(idx),
+                         flag, nflag, only.flist);
+    });
     return pasnl_launch_status();
   }
   const long sblocks = (long)((m + 63) / 64) * b;
   dim3 grid((unsigned)(nflag ? std::min(sblocks, 512L) : sblocks));
   const size_t lds = (size_t)KT_LDS_DEPTH * 3 * 64 * 4 + (size_t)((k + 7) & ~7) * 64 * 8;
-#define PASNL_KT_SEARCH(T)                                                                                                        \
-  {                                                                                                                               \
-    auto kern = knn_tree_search_kernel<T>;                                                                                        \
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                               (int)lds) != hipSuccess)                                                           \
-      return PASNL_ELAUNCH;                                                                                                       \
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, b, n, m, k, queries, clouds, stride, recs_off, static_cast<T*>(idx), flag,    \
-                       nflag, only.flist);                                                                                        \
-  }
-  if (idx_is_i64) PASNL_KT_SEARCH(long long) else PASNL_KT_SEARCH(int)
-#undef PASNL_KT_SEARCH
+  rc = with_index_type(idx_is_i64, [&](auto tag) {
+    using T = decltype(tag);
+    return launch(knn_tree_search_kernel<T>, grid, dim3(64), lds, st, b, n, m, k, queries, clouds, stride, recs_off, static_cast<T*>(idx),
+                  flag, nflag, only.flist);
+  });
+  if (rc != PASNL_OK) return rc;
   return pasnl_launch_status();
 }
 
@@ -2997,34 +2987,24 @@ extern "C" int pasnl_knn_batch_ref(int b, int n, int m, int k, const float* supp
     int* nwork = reinterpret_cast<int*>(base + L.nwork);
     const bool global = n > pasnl::KTB_LDS_NMAX;
     const size_t lds = pasnl::ktp_lds_bytes(global ? 0 : n);
-#define PASNL_KTP(T, G)                                                                                                          \
-    {                                                                                                                             \
-      auto kern = pasnl::knn_tie_path_kernel<T, G>;                                                                               \
-      if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 (int)lds) != hipSuccess)                                                         \
-        return PASNL_ELAUNCH;                                                                                                     \
-      hipLaunchKernelGGL(kern, dim3(pasnl::KTP_MAXQ), dim3(pasnl::KTB_WAVES * 64), lds, st, b, n, m, k, support, queries,          \
-                         static_cast<T*>(idx), flags.nflag, flags.flist, nwork);                                                  \
-    }
-    if (global) { if (idx_is_i64) PASNL_KTP(long long, true) else PASNL_KTP(int, true) }
-    else { if (idx_is_i64) PASNL_KTP(long long, false) else PASNL_KTP(int, false) }
-#undef PASNL_KTP
+    rc = pasnl::with_index_type(idx_is_i64, [&](auto tag) {
+      using T = decltype(tag);
+      auto kern = global ? pasnl::knn_tie_path_kernel<T, true> : pasnl::knn_tie_path_kernel<T, false>;
+      return pasnl::launch(kern, dim3(pasnl::KTP_MAXQ), dim3(pasnl::KTB_WAVES * 64), lds, st, b, n, m, k, support, queries,
+                           static_cast<T*>(idx), flags.nflag, flags.flist, nwork);
+    });
+    if (rc != PASNL_OK) return rc;
     flags.nflag = nwork;
   }
   if (small) {  // (tree + searches of a listed cloud in one workgroup, all in LDS)
     const size_t lds = pasnl::kts_lds_bytes(n);
     const int grid = std::min(b, 64);
-#define PASNL_KTS(T)                                                                                                             \
-    {                                                                                                                             \
-      auto kern = pasnl::knn_tree_small_kernel<T>;                                                                                \
-      if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 (int)lds) != hipSuccess)                                                         \
-        return PASNL_ELAUNCH;                                                                                                     \
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(pasnl::KTB_WAVES * 64), lds, st, b, n, m, k, support, queries, static_cast<T*>(idx), \
-                         depth_flag, flags.nflag, flags.flist);                                                                   \
-    }
-    if (idx_is_i64) PASNL_KTS(long long) else PASNL_KTS(int)
-#undef PASNL_KTS
+    rc = pasnl::with_index_type(idx_is_i64, [&](auto tag) {
+      using T = decltype(tag);
+      return pasnl::launch(pasnl::knn_tree_small_kernel<T>, dim3(grid), dim3(pasnl::KTB_WAVES * 64), lds, st, b, n, m, k, support,
+                           queries, static_cast<T*>(idx), depth_flag, flags.nflag, flags.flist);
+    });
+    if (rc != PASNL_OK) return rc;
     return pasnl_launch_status();
   }
   if (n > pasnl::KTB_LDS_NMAX && n <= pasnl::KTL_NMAX && k <= 64) {
@@ -3035,17 +3015,12 @@ extern "C" int pasnl_knn_batch_ref(int b, int n, int m, int k, const float* supp
     int* nwork = reinterpret_cast<int*>(base + L.nwork2);  // (its input: what the tie paths left)
     const size_t lds = pasnl::ktl_lds_bytes(n);
     const int grid = pasnl::KTL_MAXQ;  // one workgroup per listed query
-#define PASNL_KTL(T)                                                                                                             \
-    {                                                                                                                             \
-      auto kern = pasnl::knn_tree_lazy_kernel<T>;                                                                                 \
-      if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 (int)lds) != hipSuccess)                                                         \
-        return PASNL_ELAUNCH;                                                                                                     \
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(pasnl::KTB_WAVES * 64), lds, st, b, n, m, k, support, queries, static_cast<T*>(idx), \
-                         depth_flag, flags.nflag, flags.flist, nwork);                                                            \
-    }
-    if (idx_is_i64) PASNL_KTL(long long) else PASNL_KTL(int)
-#undef PASNL_KTL
+    rc = pasnl::with_index_type(idx_is_i64, [&](auto tag) {
+      using T = decltype(tag);
+      return pasnl::launch(pasnl::knn_tree_lazy_kernel<T>, dim3(grid), dim3(pasnl::KTB_WAVES * 64), lds, st, b, n, m, k, support,
+                           queries, static_cast<T*>(idx), depth_flag, flags.nflag, flags.flist, nwork);
+    });
+    if (rc != PASNL_OK) return rc;
     flags.nflag = nwork;
   }
   return pasnl::knn_tree_launch(b, n, m, k, support, queries, idx, idx_is_i64, base + L.tree, L.total - L.tree, flags, depth_flag, st);

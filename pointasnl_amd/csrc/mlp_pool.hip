@@ -203,12 +203,10 @@ static int mlp3_launch(int b, int n, int k0, const float* x, const float* w0, co
   const int k0p = (k0 + 15) & ~15;
   const int pa = (k0p > C2 ? k0p : C2) | 1;
   const size_t lds = ((size_t)32 * RB * pa + (size_t)32 * RB * (C1 + 1)) * sizeof(float);
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
-  auto kern = mlp3_pool_kernel<C1, C2, C3, RB>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
+  if (launch(mlp3_pool_kernel<C1, C2, C3, RB>, dim3((n + 32 * RB - 1) / (32 * RB), b), dim3(512), lds, st, n, k0, x, w0, b0, w1, b1,
+             w2, b2, partial) != PASNL_OK)
     return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((n + 32 * RB - 1) / (32 * RB), b), dim3(512), lds, st, n, k0, x, w0, b0, w1, b1, w2, b2, partial);
   return pasnl_launch_status();
 }
 

@@ -207,17 +207,12 @@ template <int WAVES, int PPL>
 static int fps_launch(int b, int n, int m, const float* xyz, int* idx, hipStream_t st, float* oxyz = nullptr) {
   size_t lds = (size_t)2 * 16 * 8 + (size_t)n * 16 + (size_t)m * 4;
   auto kern = fps_kernel<WAVES, PPL, 4>;
-  if (lds > 160 * 1024) {  // fall back to 12-byte records
+  if (lds > LDS_MAX_BYTES) {  // fall back to 12-byte records
     lds = (size_t)2 * 16 * 8 + (size_t)n * 12 + (size_t)m * 4;
     kern = fps_kernel<WAVES, PPL, 3>;
   }
-  if (lds > 160 * 1024) return PASNL_EUNSUPPORTED;
-  if (lds > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return PASNL_ELAUNCH;
-  }
-  hipLaunchKernelGGL(kern, dim3(b), dim3(WAVES * 64), lds, st, n, m, xyz, idx, oxyz);
+  if (lds > LDS_MAX_BYTES) return PASNL_EUNSUPPORTED;
+  if (launch(kern, dim3(b), dim3(WAVES * 64), lds, st, n, m, xyz, idx, oxyz) != PASNL_OK) return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 
@@ -438,12 +433,8 @@ static int fps_pruned_launch(int b, int n, int m, const float* xyz, int* idx, hi
   lds = (lds + 15) & ~(size_t)15;
   const size_t tail = (size_t)4096 * 4 > (size_t)(64 + m) * 4 ? (size_t)4096 * 4 : (size_t)(64 + m) * 4;
   lds += tail;
-  if (lds > 160 * 1024 - 1024 || n > 65535) return PASNL_EUNSUPPORTED;
-  auto kern = fps_pruned_kernel<WAVES, NB>;
-  if (lds > 48 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3(b), dim3(WAVES * 64), lds, st, n, m, xyz, idx, oxyz);
+  if (lds > LDS_MAX_BYTES - 1024 || n > 65535) return PASNL_EUNSUPPORTED;
+  if (launch(fps_pruned_kernel<WAVES, NB>, dim3(b), dim3(WAVES * 64), lds, st, n, m, xyz, idx, oxyz) != PASNL_OK) return PASNL_ELAUNCH;
   return pasnl_launch_status();
 }
 

@@ -142,3 +142,12 @@ def test_product_library_reads_no_environment_variable():
     makefile = open(os.path.join(csrc, "Makefile")).read()
     assert re.search(r"^[^\s#=]*tuning[^\s=]*\s*:", makefile, flags=re.M) is None
     assert "libpasnl_hip_tuning" not in open(os.path.join(ROOT, "pointasnl_amd", "_hip.py")).read()
+
+
+def test_dynamic_lds_opt_in_lives_in_one_place():
+    """Every launch with dynamic LDS goes through pasnl::launch (common.hpp), the one place that opts a kernel in above
+    the default 48 KiB: no other source file sets the attribute itself."""
+    csrc = os.path.join(ROOT, "pointasnl_amd", "csrc")
+    setters = [name for name in sorted(os.listdir(csrc)) if name.endswith((".hip", ".hpp", ".inc", ".h"))
+               and "hipFuncAttributeMaxDynamicSharedMemorySize" in open(os.path.join(csrc, name)).read()]
+    assert setters == ["common.hpp"], setters
