@@ -608,6 +608,81 @@ int pasnl_scan_reproject(long n_sub, const float* sub, long n_raw, const float* 
 int pasnl_scan_labels(long n_raw, const int* proj, const void* probs, int c, const int* lut, int nlut, unsigned* out,
                       pasnl_stream_t stream);
 
+/* ---- The ScanNet grid test and validation loops on the device (ScanNet/scannet_dataset_grid.py (D) :435-549
+ * `get_batch_gen('test' | 'validation')`, ScanNet/test_scannet_grid.py (T) :95-229 `test_cloud_segmentation` and :231-448
+ * `test_cloud_segmentation_on_val`).  S scenes live in ONE flat buffer as the scans above do: points (N,3) f32, colours
+ * (N,F) f32, potentials (N,) f64 and votes (N,C-1) FLOAT32 at the rows [offsets[i], offsets[i+1]).  The crop centre is a
+ * float64 position that is no point of the scene, so the descriptor is its own: */
+typedef struct pasnl_scene_crop {
+  long long offset;   /* first row of the scene in the flat buffers                  */
+  int cloud;          /* cloud_ind (D:483)                                            */
+  int pick;           /* point_ind inside the scene (D:484)                           */
+  int n;              /* the scene's point count                                      */
+  int k;              /* num_point + buffer of this crop (D:494-498)                  */
+  double cx, cy, cz;  /* pick_point = float64(points[pick]) + noise (D:485-489)       */
+} pasnl_scene_crop_t;
+
+/* Pick (D:483-489): the two-level argmin of pasnl_scan_pick (first index among equals, numpy's NaN rule), then
+ * centre = (double)points[offset + pick] + noise[0..3).  k: ONE device int; noise: THREE device doubles, the host's
+ * rng.normal(scale=0.35, size=(1,3)).  -> desc (one descriptor), out_cloud (one int, NULL: not wanted).  One workgroup. */
+int pasnl_scene_pick(int s, const long long* offsets, const double* potentials, const double* min_potentials,
+                     const float* points, const int* k, const double* noise, pasnl_scene_crop_t* desc, int* out_cloud,
+                     pasnl_stream_t stream);
+
+/* pasnl_knn_crop_indirect around the float64 centres of desc[0..b) (`input_trees[...].query(pick_point, k)`, D:498): the
+ * same kernels behind a template parameter, the key ((dx*dx)+(dy*dy))+(dz*dz) with dx = (double)x - cx.  With centres
+ * that are float32 values the results are bit-identical to pasnl_knn_crop_indirect.  Ties at the k-th distance go to the
+ * lowest index.  workspace: pasnl_knn_crop_workspace_bytes(b, nmax) bytes. */
+int pasnl_knn_crop_scene(int b, long nmax, const float* points, const pasnl_scene_crop_t* desc, int kcap, int* out_idx,
+                         double* out_d2, int* out_count, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
+/* pasnl_scene_pick and pasnl_knn_crop_scene for ONE crop with the pick fused into the selection's init kernel: eight
+ * launches instead of nine, the same results.  workspace: pasnl_knn_crop_workspace_bytes(1, nmax) bytes. */
+int pasnl_scene_pick_crop(int s, const long long* offsets, const double* potentials, const double* min_potentials,
+                          const float* points, const int* k, const double* noise, pasnl_scene_crop_t* desc, int* out_cloud,
+                          long nmax, int kcap, int* out_idx, double* out_d2, int* out_count, void* workspace,
+                          size_t workspace_bytes, pasnl_stream_t stream);
+
+/* The rest of the crop (D:500-501, 519-539) for b crops: rank the selected entries by (d2, index) and apply perm as
+ * pasnl_crop_order_permute does -> out_select (b,num_point) i32; then the model input out_input (b,num_point,W) f32 with
+ * W = 3 + nfeat (+ 3 if abs_coords): xyz = (float)((double)p - c); the scene's colour row (colors (N,nfeat) f32, nfeat = 0:
+ * none, colors may be NULL); abs_coords: (float)((double)xyz + c), the reference's three extra feature columns (D:539).
+ * One workgroup per crop sorts in LDS: kcap <= 14336, else PASNL_EUNSUPPORTED. */
+int pasnl_scene_order_gather(int b, const pasnl_scene_crop_t* desc, const float* points, const float* colors, int nfeat,
+                             const int* idx, const double* d2, int kcap, const int* perm, int num_point, int abs_coords,
+                             int* out_select, float* out_input, pasnl_stream_t stream);
+
+/* The potential update of one crop (D:512-516) in the reference's dtypes, as pasnl_scan_possibility_update with the
+ * distances taken against the float64 centre: dists in f32 from (float)((double)x - cx); delta = (1 - dists/max(dists))^2;
+ * potentials[idx] += (double)delta (last occurrence of a repeated index); min_potentials[cloud] = np.min of the scene.
+ * win: as in pasnl_scan_possibility_update.  ONE launch (one workgroup: maximum, update and minimum behind barriers). */
+int pasnl_scene_potential_update(int num_point, const pasnl_scene_crop_t* desc, const float* points, const int* select,
+                                 double* potentials, double* min_potentials, int* win, pasnl_stream_t stream);
+
+/* The votes of b crops (T:141-149 / 283-291), crop after crop in batch order, into the FLOAT32 table of nc = C - 1 classes:
+ * new = f32(smooth_old * old) + f32(smooth_new * probs) -- numpy's `python_float * float32_array`: smooth_old =
+ * float32(test_smooth), smooth_new = float32(1 - test_smooth), two float32 products and one float32 sum.  is_logits: values
+ * (b,num_point,nc+1) f32 and probs = softmax(values[..., 1:]) in f32 (T:95); otherwise values (b,num_point,nc) are the
+ * probabilities.  A repeated index within a crop: the last occurrence wins.  nc <= 64.  Two launches per crop. */
+int pasnl_scene_vote(int b, int num_point, int nc, const float* values, int is_logits, const int* select, const int* cloud,
+                     const long long* offsets, float smooth_old, float smooth_new, float* test_probs, int* win,
+                     pasnl_stream_t stream);
+
+/* What the reference writes per cloud at a checkpoint (T:183-218 / 316-328, 409-433), for m output points: the row
+ * r = proj[j] (NULL: j) of the scene's table probs (n,nc) f32; out_preds[j] = label_values[argmax(row with a zero inserted
+ * at every l with ignored[l] != 0)] (nl label values, the FIRST maximum, numpy's NaN rule; the caller checks nc + the number
+ * of ignored labels == nl); out_pots[j] = potentials[r] (NULL: not wanted; potentials: the SCENE's rows); out_probs (m,nc) =
+ * row (NULL: not wanted).  nl <= 64. */
+int pasnl_scene_labels(long m, const int* proj, const float* probs, int nc, const double* potentials, const int* label_values,
+                       const int* ignored, int nl, int* out_preds, double* out_pots, float* out_probs, pasnl_stream_t stream);
+
+/* sklearn.metrics.confusion_matrix(targets, preds, labels=label_values) (T:336, 395), ADDED to out (nl,nl) i64:
+ * out[i][j] += #{targets == label_values[i] and preds == label_values[j]}; a point whose target or prediction is not a
+ * listed value is dropped.  label_values distinct, nl <= 64.  Counters are private to a workgroup in LDS and flushed once
+ * with 64-bit atomics (integers: exact and order-free). */
+int pasnl_confusion_matrix(long n, const int* targets, const int* preds, const int* label_values, int nl, long long* out,
+                           pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,9 @@
 //          sum of the counts of the blocks before it: indices come out ASCENDING, deterministically, optionally with d2.
 // Eight launches, no host synchronisation, capturable; all state in the caller's workspace.
 #include <math.h>
+#include <type_traits>
 #include "common.hpp"
+#include "test_loop.hpp"
 
 namespace pasnl {
 
@@ -64,33 +66,75 @@ __device__ __forceinline__ unsigned long long cr_key(const float* __restrict__ p
   return (unsigned long long)__double_as_longlong(d2);
 }
 
-// IND (pasnl_knn_crop_indirect): crop c reads its scan's offset, point count, centre and k from desc[c] (written on the device
-// by pasnl_scan_pick); `n` is then the largest scan's count -- the stride of the key rows -- and blocks past the crop's own
-// count have nothing to do.  IND = false is the direct form, unchanged.
-__device__ __forceinline__ long cr_n(const pasnl_scan_crop_t* desc, int c, long n) { return desc ? (long)desc[c].n : n; }
+// D (pasnl_knn_crop_indirect, pasnl_knn_crop_scene): crop c reads its scan's offset, point count, centre and k from desc[c]
+// (written on the device by the pick); `n` is then the largest scan's count -- the stride of the key rows -- and blocks past
+// the crop's own count have nothing to do.  D = pasnl_scan_crop_t: a float32 centre (a point of the scan); D =
+// pasnl_scene_crop_t: a float64 centre (ScanNet's noisy pick).  D = CrDirect is the direct form, unchanged: no descriptor.
+struct CrDirect {
+  long long offset;
+  int n, k;
+  float cx, cy, cz;
+};
+template <class D>
+constexpr bool cr_ind = !std::is_same<D, CrDirect>::value;
+template <class D>
+__device__ __forceinline__ long cr_n(const D* desc, int c, long n) { return desc ? (long)desc[c].n : n; }
+
+// the start state of a crop of n keys: the k form (r2 < 0) or the radius form
+__device__ __forceinline__ CrState cr_start(long n, long k, int kcap, double r2) {
+  CrState s;
+  s.pad = 0;
+  if (r2 >= 0.0) {  // radius form: key <= bits(r2)  <=>  key < bits(r2) + 1; nothing to select by rank
+    s.prefix = (unsigned long long)__double_as_longlong(r2) + 1ull; s.shift = 0; s.r = 0; s.done = 1;
+  } else {
+    k = k < (long)kcap ? k : (long)kcap;
+    if (k <= 0) { s.prefix = 0ull; s.shift = 0; s.r = 0; s.done = 1; }
+    else if (k >= n) { s.prefix = 1ull; s.shift = 63; s.r = 0; s.done = 1; }  // every key (bit 63 is clear, NaNs included)
+    else { s.prefix = 0ull; s.shift = 63; s.r = (int)k; s.done = 0; }        // all keys match the empty prefix; k to find
+  }
+  return s;
+}
 
 // start state from k (or the radius): grid = b
-template <bool IND>
+template <class D>
 __global__ __launch_bounds__(CR_THREADS) void crop_init_kernel(long n, int kcap, const int* __restrict__ kdev, double r2,
                                                                unsigned* __restrict__ hist, CrState* __restrict__ state,
-                                                               const pasnl_scan_crop_t* __restrict__ desc) {
+                                                               const D* __restrict__ desc) {
   const int c = blockIdx.x;
-  if constexpr (IND) n = cr_n(desc, c, n);
+  if constexpr (cr_ind<D>) n = cr_n(desc, c, n);
   unsigned* h = hist + (size_t)c * CR_PASSES * CR_BINS;
   for (int i = threadIdx.x; i < CR_PASSES * CR_BINS; i += CR_THREADS) h[i] = 0u;
   if (threadIdx.x == 0) {
-    CrState s;
-    s.pad = 0;
-    if (r2 >= 0.0) {  // radius form: key <= bits(r2)  <=>  key < bits(r2) + 1; nothing to select by rank
-      s.prefix = (unsigned long long)__double_as_longlong(r2) + 1ull; s.shift = 0; s.r = 0; s.done = 1;
-    } else {
-      long k = IND ? (long)desc[c].k : (kdev ? (long)kdev[c] : (long)kcap);
-      k = k < (long)kcap ? k : (long)kcap;
-      if (k <= 0) { s.prefix = 0ull; s.shift = 0; s.r = 0; s.done = 1; }
-      else if (k >= n) { s.prefix = 1ull; s.shift = 63; s.r = 0; s.done = 1; }  // every key (bit 63 is clear, NaNs included)
-      else { s.prefix = 0ull; s.shift = 63; s.r = (int)k; s.done = 0; }        // all keys match the empty prefix; k to find
-    }
-    state[(size_t)c * (CR_PASSES + 1)] = s;
+    const long k = r2 >= 0.0 ? 0l : (cr_ind<D> ? (long)desc[c].k : (kdev ? (long)kdev[c] : (long)kcap));
+    state[(size_t)c * (CR_PASSES + 1)] = cr_start(n, k, kcap, r2);
+  }
+}
+
+// The ScanNet pick fused into the crop's init (the two-level argmin of pasnl_scan_pick, the noisy float64 centre, then the start state of crop 0 from the
+// descriptor it has just written): one workgroup of ST_THREADS.  hist == NULL: the pick alone (pasnl_scene_pick).
+__global__ __launch_bounds__(ST_THREADS) void scene_pick_init_kernel(int s, const long long* __restrict__ offsets,
+                                                                     const double* __restrict__ potentials,
+                                                                     const double* __restrict__ min_potentials,
+                                                                     const float* __restrict__ points, const int* __restrict__ k,
+                                                                     const double* __restrict__ noise,
+                                                                     pasnl_scene_crop_t* __restrict__ desc, int* __restrict__ out_cloud,
+                                                                     int kcap, unsigned* __restrict__ hist, CrState* __restrict__ state) {
+  __shared__ double shv[ST_WAVES];
+  __shared__ long shi[ST_WAVES];
+  const long cloud = st_argmin(min_potentials, s, shv, shi);
+  const long long off = offsets[cloud];
+  const long n = (long)(offsets[cloud + 1] - off);
+  const long pick = st_argmin(potentials + off, n, shv, shi);
+  if (hist)
+    for (int i = threadIdx.x; i < CR_PASSES * CR_BINS; i += ST_THREADS) hist[i] = 0u;
+  if (threadIdx.x == 0) {
+    pasnl_scene_crop_t d;
+    d.offset = off; d.cloud = (int)cloud; d.pick = (int)pick; d.n = (int)n; d.k = *k;
+    const float* c = points + (size_t)(off + (pick < 0 ? 0 : pick)) * 3;
+    d.cx = (double)c[0] + noise[0]; d.cy = (double)c[1] + noise[1]; d.cz = (double)c[2] + noise[2];  // D:485-489, float64
+    *desc = d;
+    if (out_cloud) *out_cloud = (int)cloud;
+    if (state) state[0] = cr_start(n, (long)d.k, kcap, -1.0);
   }
 }
 
@@ -142,11 +186,11 @@ __device__ __forceinline__ CrState cr_advance(int p, const CrState prev, const u
 }
 
 // pass P: grid = (nblk, b)
-template <int P, bool IND>
+template <int P, class D>
 __global__ __launch_bounds__(CR_THREADS) void crop_pass_kernel(long n, long scan_stride, const float* __restrict__ points,
                                                                const float* __restrict__ centres, unsigned long long* __restrict__ keys,
                                                                unsigned* __restrict__ hist, CrState* __restrict__ state,
-                                                               const pasnl_scan_crop_t* __restrict__ desc) {
+                                                               const D* __restrict__ desc) {
   __shared__ unsigned lh[CR_BINS];
   __shared__ int sh[CR_THREADS / 64 + 3];
   const int c = blockIdx.y, tid = threadIdx.x;
@@ -165,7 +209,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_pass_kernel(long n, long scan
     // k <= 0, k >= n or the radius form: only the keys are needed
   }
   unsigned long long* kc = keys + (size_t)c * n;
-  if constexpr (IND) {
+  if constexpr (cr_ind<D>) {
     n = cr_n(desc, c, n);
     if ((long)blockIdx.x * CR_BLOCK >= n) return;  // (uniform) a block past this crop's scan
   }
@@ -173,9 +217,10 @@ __global__ __launch_bounds__(CR_THREADS) void crop_pass_kernel(long n, long scan
   __syncthreads();
   const long i0 = (long)blockIdx.x * CR_BLOCK + (long)tid * CR_ITEMS;
   if constexpr (P == 0) {
-    const float* pc = IND ? points + (size_t)desc[c].offset * 3 : points + (size_t)c * scan_stride * 3;
-    const float* cc = IND ? &desc[c].cx : centres + c * 3;
-    const double cx = (double)cc[0], cy = (double)cc[1], cz = (double)cc[2];
+    const float* pc = cr_ind<D> ? points + (size_t)desc[c].offset * 3 : points + (size_t)c * scan_stride * 3;
+    double cx, cy, cz;
+    if constexpr (cr_ind<D>) { cx = (double)desc[c].cx; cy = (double)desc[c].cy; cz = (double)desc[c].cz; }
+    else { cx = (double)centres[c * 3]; cy = (double)centres[c * 3 + 1]; cz = (double)centres[c * 3 + 2]; }
 #pragma unroll
     for (int e = 0; e < CR_ITEMS; ++e) {
       const long i = i0 + e;
@@ -210,10 +255,10 @@ __device__ __forceinline__ CrState cr_final(const CrState* __restrict__ st, cons
   return cr_advance(CR_PASSES, s, hist_c + (size_t)(CR_PASSES - 1) * CR_BINS, sh);
 }
 
-template <bool IND>
+template <class D>
 __global__ __launch_bounds__(CR_THREADS) void crop_count_kernel(long n, const unsigned long long* __restrict__ keys,
                                                                 const unsigned* __restrict__ hist, CrState* __restrict__ state,
-                                                                int* __restrict__ blk, const pasnl_scan_crop_t* __restrict__ desc) {
+                                                                int* __restrict__ blk, const D* __restrict__ desc) {
   __shared__ int sh[CR_THREADS / 64 + 3];
   __shared__ int tot[2];
   const int c = blockIdx.y, tid = threadIdx.x;
@@ -223,7 +268,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_count_kernel(long n, const un
   if (tid < 2) tot[tid] = 0;
   __syncthreads();
   const unsigned long long* kc = keys + (size_t)c * n;
-  if constexpr (IND) n = cr_n(desc, c, n);
+  if constexpr (cr_ind<D>) n = cr_n(desc, c, n);
   const long i0 = (long)blockIdx.x * CR_BLOCK + (long)tid * CR_ITEMS;
   int below = 0, on = 0;
 #pragma unroll
@@ -242,11 +287,11 @@ __global__ __launch_bounds__(CR_THREADS) void crop_count_kernel(long n, const un
   if (tid < 2) blk[((size_t)c * gridDim.x + blockIdx.x) * 2 + tid] = tot[tid];
 }
 
-template <bool IND>
+template <class D>
 __global__ __launch_bounds__(CR_THREADS) void crop_write_kernel(long n, int kcap, const unsigned long long* __restrict__ keys,
                                                                 const CrState* __restrict__ state, const int* __restrict__ blk,
                                                                 int* __restrict__ out_idx, double* __restrict__ out_d2,
-                                                                int* __restrict__ out_count, const pasnl_scan_crop_t* __restrict__ desc) {
+                                                                int* __restrict__ out_count, const D* __restrict__ desc) {
   __shared__ int shb[2][CR_THREADS / 64];
   __shared__ int base[2];
   const int c = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -268,7 +313,7 @@ __global__ __launch_bounds__(CR_THREADS) void crop_write_kernel(long n, int kcap
     }
   }
   const unsigned long long* kc = keys + (size_t)c * n;
-  if constexpr (IND) n = cr_n(desc, c, n);
+  if constexpr (cr_ind<D>) n = cr_n(desc, c, n);
   const long i0 = (long)blockIdx.x * CR_BLOCK + (long)tid * CR_ITEMS;
   unsigned long long key[CR_ITEMS];
   int below = 0, on = 0;
@@ -303,19 +348,20 @@ __global__ __launch_bounds__(CR_THREADS) void crop_write_kernel(long n, int kcap
   }
 }
 
-template <bool IND>
+template <class D>
 static void cr_launch(int b, long n, long scan_stride, const float* points, const float* centres, const int* k, int kcap, double r2,
-                      int* out_idx, double* out_d2, int* out_count, const CrWs& w, const pasnl_scan_crop_t* desc, hipStream_t s) {
+                      int* out_idx, double* out_d2, int* out_count, const CrWs& w, const D* desc, hipStream_t s, bool init = true) {
+  // init = false: the start state and the zeroed histograms are already enqueued (pasnl_scene_pick_crop's fused pick)
   const long nblk = (n + CR_BLOCK - 1) / CR_BLOCK;
-  hipLaunchKernelGGL(crop_init_kernel<IND>, dim3(b), dim3(CR_THREADS), 0, s, n, kcap, k, r2, w.hist, w.state, desc);
+  if (init) hipLaunchKernelGGL(crop_init_kernel<D>, dim3(b), dim3(CR_THREADS), 0, s, n, kcap, k, r2, w.hist, w.state, desc);
   const dim3 grid((unsigned)nblk, (unsigned)b);
-  hipLaunchKernelGGL((crop_pass_kernel<0, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
-  hipLaunchKernelGGL((crop_pass_kernel<1, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
-  hipLaunchKernelGGL((crop_pass_kernel<2, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
-  hipLaunchKernelGGL((crop_pass_kernel<3, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
-  hipLaunchKernelGGL((crop_pass_kernel<4, IND>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
-  hipLaunchKernelGGL(crop_count_kernel<IND>, grid, dim3(CR_THREADS), 0, s, n, w.keys, w.hist, w.state, w.blk, desc);
-  hipLaunchKernelGGL(crop_write_kernel<IND>, grid, dim3(CR_THREADS), 0, s, n, kcap, w.keys, w.state, w.blk, out_idx, out_d2, out_count, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<0, D>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<1, D>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<2, D>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<3, D>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL((crop_pass_kernel<4, D>), grid, dim3(CR_THREADS), 0, s, n, scan_stride, points, centres, w.keys, w.hist, w.state, desc);
+  hipLaunchKernelGGL(crop_count_kernel<D>, grid, dim3(CR_THREADS), 0, s, n, w.keys, w.hist, w.state, w.blk, desc);
+  hipLaunchKernelGGL(crop_write_kernel<D>, grid, dim3(CR_THREADS), 0, s, n, kcap, w.keys, w.state, w.blk, out_idx, out_d2, out_count, desc);
 }
 
 }  // namespace pasnl
@@ -338,7 +384,7 @@ extern "C" int pasnl_knn_crop(int b, long n, long scan_stride, const float* poin
   PASNL_REQUIRE(workspace_bytes >= cr_layout(b, n, static_cast<char*>(workspace), &w), PASNL_EWORKSPACE);
   hipStream_t s = pasnl_hip_stream(stream);
   const double r2 = radius > 0.0 ? radius * radius : -1.0;  // sklearn: reduced radius r*r in double, inclusive
-  cr_launch<false>(b, n, scan_stride, points, centres, k, kcap, r2, out_idx, out_d2, out_count, w, nullptr, s);
+  cr_launch<CrDirect>(b, n, scan_stride, points, centres, k, kcap, r2, out_idx, out_d2, out_count, w, nullptr, s);
   return pasnl_launch_status();
 }
 
@@ -348,6 +394,44 @@ extern "C" int pasnl_knn_crop_indirect(int b, long nmax, const float* points, co
   PASNL_REQUIRE(points && desc && out_idx && out_count && workspace, PASNL_ENULL);
   CrWs w;
   PASNL_REQUIRE(workspace_bytes >= cr_layout(b, nmax, static_cast<char*>(workspace), &w), PASNL_EWORKSPACE);
-  cr_launch<true>(b, nmax, 0, points, nullptr, nullptr, kcap, -1.0, out_idx, out_d2, out_count, w, desc, pasnl_hip_stream(stream));
+  cr_launch<pasnl_scan_crop_t>(b, nmax, 0, points, nullptr, nullptr, kcap, -1.0, out_idx, out_d2, out_count, w, desc, pasnl_hip_stream(stream));
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_knn_crop_scene(int b, long nmax, const float* points, const pasnl_scene_crop_t* desc, int kcap, int* out_idx,
+                                    double* out_d2, int* out_count, void* workspace, size_t workspace_bytes, pasnl_stream_t stream) {
+  PASNL_REQUIRE(b > 0 && nmax > 0 && nmax < (1l << 31) && kcap > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(points && desc && out_idx && out_count && workspace, PASNL_ENULL);
+  CrWs w;
+  PASNL_REQUIRE(workspace_bytes >= cr_layout(b, nmax, static_cast<char*>(workspace), &w), PASNL_EWORKSPACE);
+  cr_launch<pasnl_scene_crop_t>(b, nmax, 0, points, nullptr, nullptr, kcap, -1.0, out_idx, out_d2, out_count, w, desc,
+                                pasnl_hip_stream(stream));
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_scene_pick(int s, const long long* offsets, const double* potentials, const double* min_potentials,
+                                const float* points, const int* k, const double* noise, pasnl_scene_crop_t* desc, int* out_cloud,
+                                pasnl_stream_t stream) {
+  PASNL_REQUIRE(s > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(offsets && potentials && min_potentials && points && k && noise && desc, PASNL_ENULL);
+  hipLaunchKernelGGL(scene_pick_init_kernel, dim3(1), dim3(ST_THREADS), 0, pasnl_hip_stream(stream), s, offsets, potentials,
+                     min_potentials, points, k, noise, desc, out_cloud, 0, (unsigned*)nullptr, (CrState*)nullptr);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_scene_pick_crop(int s, const long long* offsets, const double* potentials, const double* min_potentials,
+                                     const float* points, const int* k, const double* noise, pasnl_scene_crop_t* desc,
+                                     int* out_cloud, long nmax, int kcap, int* out_idx, double* out_d2, int* out_count,
+                                     void* workspace, size_t workspace_bytes, pasnl_stream_t stream) {
+  PASNL_REQUIRE(s > 0 && nmax > 0 && nmax < (1l << 31) && kcap > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(offsets && potentials && min_potentials && points && k && noise && desc, PASNL_ENULL);
+  PASNL_REQUIRE(out_idx && out_count && workspace, PASNL_ENULL);
+  CrWs w;
+  PASNL_REQUIRE(workspace_bytes >= cr_layout(1, nmax, static_cast<char*>(workspace), &w), PASNL_EWORKSPACE);
+  hipStream_t st = pasnl_hip_stream(stream);
+  hipLaunchKernelGGL(scene_pick_init_kernel, dim3(1), dim3(ST_THREADS), 0, st, s, offsets, potentials, min_potentials, points, k,
+                     noise, desc, out_cloud, kcap, w.hist, w.state);
+  cr_launch<pasnl_scene_crop_t>(1, nmax, 0, points, nullptr, nullptr, kcap, -1.0, out_idx, out_d2, out_count, w,
+                                (const pasnl_scene_crop_t*)desc, st, false);
   return pasnl_launch_status();
 }

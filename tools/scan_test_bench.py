@@ -8,7 +8,7 @@ VariableStore, B = 8, num_point = 10240) over synthetic lidar-like scans of ~1e5
 Prints one JSON line: crops/s of both, their ratio, the device chain's us per crop (HIP events around next_batch alone)
 and the reprojection's us per 120k-point raw scan.
 
-  python tools/scan_test_bench.py [--scans 8] [--points 100000] [--batches 6] [--warmup 2]
+  python tools/scan_test_bench.py [--scans 8] [--points 100000] [--batches 6] [--warmup 2] [--batch 8] [--num-point 10240]
 """
 import argparse
 import json
@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--batches", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--num-point", type=int, default=10240)
     args = ap.parse_args()
 
     from pointasnl_amd.models import pointasnl_sem_seg_res
@@ -48,7 +49,7 @@ def main():
     from pointasnl_amd.utils import tf_util
 
     torch.cuda.set_device(0)
-    B, NP, NB, C = args.batch, 10240, 1024, 20
+    B, NP, NB, C = args.batch, args.num_point, 1024, 20
     scans = [lidar(1000 + i, args.points + 997 * i) for i in range(args.scans)]
     tf_util.set_store(tf_util.VariableStore(seed=5))
 
