@@ -683,6 +683,68 @@ int pasnl_scene_labels(long m, const int* proj, const float* probs, int nc, cons
 int pasnl_confusion_matrix(long n, const int* targets, const int* preds, const int* label_values, int nl, long long* out,
                            pasnl_stream_t stream);
 
+/* ---- The ScanNet sliding-window whole-scene test loop on the device (ScanNet/scannet_dataset.py (D) :183-300
+ * `ScannetDatasetWholeSceneSlidingWindow.__getitem__`, ScanNet/test_scannet.py (T) :96-103 `add_vote` and :107-196
+ * `eval_one_epoch`).  One scene at a time: xyz (n,3) f32 is the scene's OWN buffer, moved in place vote after vote as the
+ * reference moves scene_points_list[index]; colours (n,nfeat) f32 never move.  The numpy RNG stream and the merge of small
+ * blocks (D:244-269, over counts and centres only) stay on the host.  n <= 2^30; coordinates are finite. */
+
+/* The noise step (D:192-212).  centroid = np.mean(xyz, axis=0) as numpy computes it for a float32 (n,3) view: per column ONE
+ * float32 sum in index order (a dependent chain: tiles staged in LDS, the x, y and z chains in three lanes), divided by
+ * float32(n); max_length = max(|max|, |min|) of the float32 xyz - centroid over all three columns.  Then for every draw j
+ * with last[j] != 0: i = choices[j], xyz[i] = float32((float64(float32((xyz[i] - centroid) / max_length)) + shift[j]) *
+ * float64(max_length) + float64(centroid)) and stamp[i] = serial (semantic_seg_ini[choices] = 0 for this call: a label reads
+ * as 0 while its stamp equals the call's serial).  choices (m) i32 in [0,n): the host's rng.choice(n, m); shift (m,3) f64:
+ * (rng.randn(m,3) - 0.5) / 0.5 * 0.002; last (m) u8: 1 where no later draw names the same point (numpy's fancy assignment
+ * keeps that one; every value is read before any store).  -> stats[0..3) centroid, stats[3] max_length (device floats).
+ * Two launches. */
+int pasnl_window_noise(long n, float* xyz, int m, const int* choices, const double* shift, const unsigned char* last, int serial,
+                       int* stamp, float* stats, pasnl_stream_t stream);
+
+/* coordmin / coordmax (D:214-215): out_bounds[0..3) = np.min(xyz, axis=0), out_bounds[3..6) = np.max(xyz, axis=0).  One
+ * workgroup. */
+int pasnl_window_bounds(long n, const float* xyz, float* out_bounds, pasnl_stream_t stream);
+
+/* Window membership (D:223-233), counted.  Window w = i * ny + j (i < nx, j < ny, the reference's loop order) has
+ * curmin = float64(coordmin) + [i * delta, j * delta, 0] and curmax = curmin + [1.5, 1.5, float32(coordmax_z - coordmin_z)];
+ * a point is a member when its float32 coordinates are >= curmin - 0.2 and <= curmax + 0.2 on all three axes, compared in
+ * float64 exactly so (every window of an axis is tested: no index comes out of a division).  bounds: the six device floats
+ * of pasnl_window_bounds.  hist: pasnl_window_hist_bytes(n, nx, ny) device bytes -- per window and chunk of 64 consecutive
+ * points the member count (a wave ballot), then scanned in place per window to the count in earlier chunks; it is the input
+ * of pasnl_window_fill.  -> out_counts (nx*ny) i32, empty windows included.  nx, ny <= 64, else PASNL_EUNSUPPORTED.  Two
+ * launches. */
+size_t pasnl_window_hist_bytes(long n, int nx, int ny);
+int pasnl_window_count(long n, const float* xyz, const float* bounds, int nx, int ny, double delta, int* hist, int* out_counts,
+                       pasnl_stream_t stream);
+
+/* The member lists (D:229-241), each written straight to its place in the concatenation the host's merge decided
+ * (D:263-268): window w's members, in ascending scene index, go to out_idx[woff[w] ...] (woff (nx*ny) i32, -1: skip the
+ * window), and out_mask[...] is the 0.001-margin test of D:234 (the sample weight of every split but 'train').  A member's
+ * rank is its chunk's scanned count plus the members among the lower lanes of its wave: deterministic, no arrival order.
+ * cap: the length of out_idx / out_mask (nothing is written at or past it). */
+int pasnl_window_fill(long n, const float* xyz, const float* bounds, int nx, int ny, double delta, const int* hist, const int* woff,
+                      long cap, int* out_idx, unsigned char* out_mask, pasnl_stream_t stream);
+
+/* Rows (D:271-300): rowpos (real_rows,block_points) i32 holds, per row entry, the position in the concatenated lists that
+ * the host's shuffles chose (D:281-289); entry e gets i = cat_idx[rowpos[e]] and out_data[e] = xyz[i] | rgb[i] (3 + nfeat
+ * f32), out_label[e] = labels[i], or 0 where stamp[i] == serial (D:211), out_weight[e] = cat_mask[rowpos[e]] (i32 0/1),
+ * out_idx[e] = i.  Rows real_rows..rows-1 are written as zeros: the reference leaves stale data in the unused rows of a
+ * scene's last batch (T:147-150) and never votes them. */
+int pasnl_window_gather(int rows, int real_rows, int block_points, const int* rowpos, long cap, const int* cat_idx,
+                        const unsigned char* cat_mask, long n, const float* xyz, const float* rgb, int nfeat, const int* labels,
+                        const int* stamp, int serial, float* out_data, int* out_label, int* out_weight, int* out_idx,
+                        pasnl_stream_t stream);
+
+/* The vote (T:159-161 with add_vote, T:96-103): for every entry with weight != 0, pred = argmax(logits[e][1:]) + 1 (the
+ * FIRST maximum, numpy's NaN rule) and pool[idx[e]][pred] += 1.  logits (rows,block_points,c) f32; pool (n,c) i32: integer
+ * counters, exact and order-free (no float atomics).  c >= 2. */
+int pasnl_window_vote(int rows, int block_points, int c, const float* logits, const int* idx, const int* weight, long n, int* pool,
+                      pasnl_stream_t stream);
+
+/* pred_label = np.argmax(vote_label_pool, 1) (T:163): the FIRST maximum of every row of pool (n,c) i32; a row without a
+ * vote gives 0.  The counts of T:164-170 follow from pasnl_confusion_matrix over (labels, pred_label). */
+int pasnl_window_pool_labels(long n, int c, const int* pool, int* out_labels, pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
