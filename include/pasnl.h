@@ -745,6 +745,46 @@ int pasnl_window_vote(int rows, int block_points, int c, const float* logits, co
  * vote gives 0.  The counts of T:164-170 follow from pasnl_confusion_matrix over (labels, pred_label). */
 int pasnl_window_pool_labels(long n, int c, const int* pool, int* out_labels, pasnl_stream_t stream);
 
+/* ---- The SemanticKITTI sliding-window whole-scan test loop on the device (SemanticKITTI/semantic_kitti_dataset.py (D)
+ * :278-355 `SemanticKittiDatasetSlidingWindow.__getitem__`, SemanticKITTI/test_semantic_kitti.py (T) :99-105 `add_vote` and
+ * :108-231 `eval_one_epoch`).  One scan at a time: xyz (n,3) f32 never moves (there is no noise step), remission (n) f32 is
+ * optional.  coordmin / coordmax (D:289-290) come from pasnl_window_bounds, the vote (T:166, T:99-105) is pasnl_window_vote
+ * with a weight buffer of ones and final_preds (T:174-175) is pasnl_window_pool_labels: both are general in c.  The numpy RNG
+ * stream and the merge of small blocks (D:311-327, over counts and centres only, empty windows included) stay on the host.
+ * n <= 2^30; coordinates are finite. */
+
+/* Window membership (D:296-302), counted.  Window w = i * ny + j (i < nx, j < ny, the reference's loop order) has
+ * curmin = float64(coordmin) + [i * stride, j * stride, 0] and curmax = curmin + [block, block, float64(float32(coordmax_z -
+ * coordmin_z))]; a point is a member when its float32 coordinates, widened to float64, are >= curmin - 0.2 and <= curmax +
+ * 0.2 on all three axes (every window of an axis is tested with exactly these comparisons: no index comes out of a
+ * division; along an axis the members are one contiguous range lo..hi because both bounds are monotone in i).  bounds: the
+ * six device floats of pasnl_window_bounds.  hist: pasnl_kwindow_hist_bytes(n, nx, ny) device bytes -- cleared, then per
+ * window and chunk of 64 consecutive points the member count (a wave ballot; a wave stores only for the windows inside the
+ * rectangle of its points' ranges that hold one of them), then scanned in place per window to the count in earlier chunks; it
+ * is the input of pasnl_kwindow_fill.  -> out_counts (nx*ny) i32, 0 for an empty window.  No limit per axis: nx * ny <=
+ * INT_MAX, else PASNL_EUNSUPPORTED (pasnl_kwindow_hist_bytes: 0).  A clear and two launches. */
+size_t pasnl_kwindow_hist_bytes(long n, int nx, int ny);
+int pasnl_kwindow_count(long n, const float* xyz, const float* bounds, int nx, int ny, double block, double stride, int* hist,
+                        int* out_counts, pasnl_stream_t stream);
+
+/* The member lists (D:300-307, curchoice_idx), each written straight to its place in the concatenation the host's merge
+ * decided (D:325-326): window w's members, in ascending scan index, go to out_idx[woff[w] ...] (woff (nx*ny) i32, -1: skip
+ * the window).  A member's rank is its chunk's scanned count plus the members among the lower lanes of its wave:
+ * deterministic, no arrival order.  cap: the length of out_idx (nothing is written at or past it). */
+int pasnl_kwindow_fill(long n, const float* xyz, const float* bounds, int nx, int ny, double block, double stride, const int* hist,
+                       const int* woff, long cap, int* out_idx, pasnl_stream_t stream);
+
+/* Rows (D:334-351) as a batch is fed (T:149-161): rowpos (real_rows,block_points) i32 holds, per row entry, the position in
+ * the concatenated lists that the host's shuffles chose (D:337-345); entry e gets i = cat_idx[rowpos[e]], out_data[e] =
+ * xyz[i] followed by remission[i] when nfeat == 1 (3 + nfeat f32; nfeat is 0 or 1) and out_idx[e] = i.  Rows
+ * real_rows..rows-1 are written as zeros: the reference leaves stale data in the unused rows of a scan's last batch (T:157)
+ * and never votes them.  angles (rows) f64 or NULL: rotate_point_cloud_z (utils/provider.py:71-89) per row, xyz @ [[cos, sin,
+ * 0], [-sin, cos, 0], [0, 0, 1]] computed in float64 from the cos and sin of the host's angle and rounded to float32 (within
+ * one float32 ulp of numpy's product, whose dgemm fixes no summation order). */
+int pasnl_kwindow_gather(int rows, int real_rows, int block_points, const int* rowpos, long cap, const int* cat_idx, long n,
+                         const float* xyz, const float* remission, int nfeat, const double* angles, float* out_data, int* out_idx,
+                         pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ SYMBOLS = [
     "pasnl_scan_pick", "pasnl_knn_crop_indirect", "pasnl_crop_order_permute", "pasnl_scan_possibility_update", "pasnl_scan_scratch_init", "pasnl_scan_vote", "pasnl_scan_reproject_workspace_bytes", "pasnl_scan_reproject", "pasnl_scan_labels",
     "pasnl_scene_pick", "pasnl_knn_crop_scene", "pasnl_scene_pick_crop", "pasnl_scene_order_gather", "pasnl_scene_potential_update", "pasnl_scene_vote", "pasnl_scene_labels", "pasnl_confusion_matrix",
     "pasnl_window_noise", "pasnl_window_bounds", "pasnl_window_hist_bytes", "pasnl_window_count", "pasnl_window_fill", "pasnl_window_gather", "pasnl_window_vote", "pasnl_window_pool_labels",
+    "pasnl_kwindow_hist_bytes", "pasnl_kwindow_count", "pasnl_kwindow_fill", "pasnl_kwindow_gather",
     "pasnl_grad_workspace_bytes", "pasnl_gather_point_grad_det", "pasnl_group_point_grad_det", "pasnl_three_interpolate_grad_det",
 ]
 
@@ -64,6 +65,7 @@ def lib():
         _lib.pasnl_scan_reproject_workspace_bytes.restype = ctypes.c_size_t
         _lib.pasnl_nl_attention_workspace_bytes.restype = ctypes.c_size_t
         _lib.pasnl_window_hist_bytes.restype = ctypes.c_size_t
+        _lib.pasnl_kwindow_hist_bytes.restype = ctypes.c_size_t
         for s in SYMBOLS:
             getattr(_lib, s)  # AttributeError here == header / library mismatch
     return _lib

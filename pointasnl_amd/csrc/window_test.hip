@@ -14,6 +14,7 @@
 #include <math.h>
 #include "common.hpp"
 #include "test_loop.hpp"
+#include "window_scan.hpp"
 
 namespace pasnl {
 
@@ -198,33 +199,7 @@ __global__ __launch_bounds__(64 * WW_WAVES) void window_count_kernel(long n, con
   }
 }
 
-// pass 2: per window an exclusive scan over the chunks, in place; counts[w] = the window's size
-__global__ __launch_bounds__(256) void window_scan_kernel(long nchunks, int* __restrict__ hist, int* __restrict__ counts) {
-  __shared__ int wsum[4];
-  int* row = hist + (size_t)blockIdx.x * nchunks;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int carry = 0;
-  for (long base = 0; base < nchunks; base += 256) {
-    const long k = base + threadIdx.x;
-    const int v = k < nchunks ? row[k] : 0;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int w = 0; w < 4; ++w) {
-      before += w < wave ? wsum[w] : 0;
-      all += wsum[w];
-    }
-    if (k < nchunks) row[k] = carry + before + inc - v;
-    carry += all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[blockIdx.x] = carry;
-}
+// pass 2 is window_scan_kernel (window_scan.hpp): per window an exclusive scan over the chunks, in place
 
 // pass 3: a member's place is woff[w] + (members in earlier chunks) + (members among the lower lanes): ascending scene index
 __global__ __launch_bounds__(64 * WW_WAVES) void window_fill_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
@@ -314,9 +289,6 @@ __global__ __launch_bounds__(256) void window_pool_labels_kernel(long n, int c, 
 }  // namespace pasnl
 
 using namespace pasnl;
-
-static inline unsigned wt_blocks(long n, int t) { return (unsigned)((n + t - 1) / t); }
-static inline long wt_chunks(long n) { return (n + 63) / 64; }
 
 extern "C" int pasnl_window_noise(long n, float* xyz, int m, const int* choices, const double* shift, const unsigned char* last,
                                   int serial, int* stamp, float* stats, pasnl_stream_t stream) {
