@@ -785,6 +785,58 @@ int pasnl_kwindow_gather(int rows, int real_rows, int block_points, const int* r
                          const float* xyz, const float* remission, int nfeat, const double* angles, float* out_data, int* out_idx,
                          pasnl_stream_t stream);
 
+/* ---- The ModelNet40 classification evaluation loop on the device (modelnet_dataset.py (D) :9-37 `pc_normalize` and
+ * `farthest_point_sample`, :79-136 `_get_item` / `next_batch`; test.py (T) :105-174 `eval_one_epoch`; utils/provider.py (P)
+ * :8-24 `normalize_data`).  All raw shapes live in one flat (total_rows, ld) f32 buffer, shape `id` at rows row0[id] ..
+ * row0[id] + nraw[id]; the prepared set is (n_shapes, npoint, ch) f32 beside it.  The numpy RNG stream stays on the host.
+ * Coordinates are finite. */
+
+/* farthest_point_sample (D:16-37) for s raw shapes at once, one workgroup each: NOT the TF sampler of
+ * pasnl_farthest_point_sample (start 0, another tie rule).  Call-shape j is shape ids[j] (ids NULL: j) and starts at
+ * start[j], the host's randint(0, N).  float32 as numpy runs it on the float32 rows: dx = x - cx, d = (dx*dx + dy*dy) + dz*dz
+ * without contraction, the running distance starts at 1e10 and is replaced only by a strictly smaller d, the next pick is
+ * np.argmax (the FIRST index among equal maxima).  Columns 0..2 of the ld-wide rows are read.  -> out_idx (n_shapes,npoint)
+ * i32 and / or out_rows (n_shapes,npoint,out_ld) f32, the picked rows' first out_ld columns (point[centroids]); both are
+ * indexed by the shape's id; either may be NULL.  n_min / n_max: the smallest and largest nraw among the shapes of the call,
+ * as the host knows them (a shape outside them, or outside its buffer, is skipped): npoint > n_min -> PASNL_EINVAL (the
+ * reference fails at the batch assignment); n_max > pasnl_modelnet_fps_cap() = 12288 rows, what fits the workgroup's LDS ->
+ * PASNL_EUNSUPPORTED (T:50 asserts NUM_POINT <= 10000, the raw shapes' size). */
+int pasnl_modelnet_fps_cap(void);
+int pasnl_modelnet_fps(int s, int npoint, int ld, long n_shapes, const int* ids, const long* row0, const int* nraw, const int* start,
+                       int n_min, int n_max, long total_rows, const float* raw, int* out_idx, float* out_rows, int out_ld,
+                       pasnl_stream_t stream);
+
+/* pc_normalize (D:9-14) in place on columns 0..2 of s shapes (ids[j], or j) of data (n_shapes,npoint,ld) f32, numpy's bits:
+ * centroid = per column ONE float32 sum down the rows divided by float32(npoint) (np.mean(axis=0), the chain of
+ * pasnl_window_noise), pc - centroid, m = max(sqrt((x*x + y*y) + z*z)) in float32, pc / m.  One workgroup per shape. */
+int pasnl_modelnet_normalize(int s, int npoint, int ld, long n_shapes, const int* ids, float* data, pasnl_stream_t stream);
+
+/* next_batch into the persistent batch (D:124-136, T:135-136): row i < bsize of batch (b,npoint,ch) f32 becomes prepared shape
+ * order[start + i] and labels[i] (b) i32 its class shape_labels[...]; rows bsize..b-1 of both are NOT touched -- in the last
+ * batch of an epoch they still hold the batch before it, as in the reference.  order (n_order) i32: the dataset's idxs.  ch is
+ * 3 or 6. */
+int pasnl_modelnet_batch(int b, int bsize, int npoint, int ch, const int* order, long n_order, long start, long n_shapes,
+                         const float* prepared, const int* shape_labels, float* batch, int* labels, pasnl_stream_t stream);
+
+/* The noisy points (T:129-132 with normalize_data, P:8-24): uniforms (bsize,k,3) f64 as the host drew them; each (k,3) block
+ * is normalised in float64 -- per column one sum down the rows / float64(k), subtracted, divided by
+ * max(sqrt((x*x + y*y) + z*z)) -- rounded to float32 (the feed into a float32 placeholder) and written to rows 0..k-1,
+ * columns 0..2 of batch rows 0..bsize-1.  Other columns and rows are not touched.  k = 1 gives 0/0 = NaN, as numpy does.
+ * 1 <= k <= npoint. */
+int pasnl_modelnet_noise(int bsize, int k, const double* uniforms, int npoint, int ch, float* batch, pasnl_stream_t stream);
+
+/* One vote (T:147-149): sums (b,c) f64 += float64(logits (b,c) f32) over ALL b rows (numpy's float64 += float32), and
+ * loss[1] += the batch's mean sparse-softmax cross-entropy over all b rows, stale ones included (a log-sum-exp shifted by the
+ * row maximum in float32, the mean in float64: compared under a tolerance, never by bits).  loss: two f64, {loss_sum,
+ * loss_vote}. */
+int pasnl_cls_vote(int b, int c, const float* logits, const int* labels, double* sums, double* loss, pasnl_stream_t stream);
+
+/* The end of a batch (T:150-162): preds[i] = np.argmax(sums[i]) (the FIRST maximum) for rows i < bsize; totals[0]
+ * (total_correct) += matches, totals[1] (total_seen) += bsize, totals[2] (total_object) += b; seen_class / correct_class (c)
+ * count the rows' labels; loss[0] += loss[1] / num_votes and loss[1] = 0; sums are cleared.  All counters i64. */
+int pasnl_cls_tally(int b, int bsize, int c, int num_votes, const int* labels, double* sums, long long* totals, long long* seen_class,
+                    long long* correct_class, int* preds, double* loss, pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ Layout mirrors the reference so its ``sys.path`` idiom keeps working (utils/poin
     tf_ops/3d_interpolation/tf_interpolate.py three_nn, three_interpolate
     utils/nearest_neighbors/lib/python/nearest_neighbors.py   knn_batch, knn
     utils/pointasnl_util.py, utils/pointnet_util.py, utils/tf_util.py, models/*.py   (torch host mirror)
+    modelnet_dataset.py                       ModelNetDataset (the reference imports it from its root directory)
     csrc/                                     hand-written HIP kernels + the C ABI (include/pasnl.h)
 
 ``install_paths()`` appends those directories to ``sys.path`` so that ``import tf_sampling`` etc. resolve
@@ -50,4 +51,5 @@ def _load(name, *parts):
 tf_sampling = _load("tf_sampling", "tf_ops", "sampling", "tf_sampling.py")
 tf_grouping = _load("tf_grouping", "tf_ops", "grouping", "tf_grouping.py")
 tf_interpolate = _load("tf_interpolate", "tf_ops", "3d_interpolation", "tf_interpolate.py")
+modelnet_dataset = _load("modelnet_dataset", "modelnet_dataset.py")
 from .utils.nearest_neighbors.lib.python import nearest_neighbors  # noqa: E402

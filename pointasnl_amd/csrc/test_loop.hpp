@@ -64,6 +64,24 @@ __device__ __forceinline__ double st_min(const double* __restrict__ p, long n, d
 }
 
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (a > b ? a : b); }
+__device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a > b ? a : b); }
+
+// np.mean(axis=0) of an (N,3) array is, per column, ONE sum in row order: a dependent chain of N adds.  This continues the
+// chain `acc` of column `col` down rows [0, cnt) of a 3-wide row-major tile (the loads go eight at a time ahead of the adds;
+// the adds stay in order).  A chain starts at -0: -0 + x == x for every x, so it starts at the first row as numpy's does.
+template <typename T>
+__device__ __forceinline__ T st_chain3(T acc, const T* tile, int cnt, int col) {
+  int k = 0;
+  for (; k + 8 <= cnt; k += 8) {
+    T v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = tile[(k + u) * 3 + col];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc = acc + v[u];
+  }
+  for (; k < cnt; ++k) acc = acc + tile[k * 3 + col];
+  return acc;
+}
 
 // ---- order / permute: bitonic sort of (d2 bits, position) in LDS.  The flipped-merge form sorts any count m without padding:
 // a partner at or past m would be +inf and never moves, so those compare-exchanges are skipped.

@@ -50,15 +50,7 @@ __global__ __launch_bounds__(ST_THREADS) void window_centroid_kernel(long n, con
     if (tid < 3) {
       const long left = n - base / 3;
       const int cnt = left < WT_TILE ? (int)left : WT_TILE;
-      int k = 0;
-      for (; k + 8 <= cnt; k += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = tile[(k + u) * 3 + tid];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc = acc + v[u];
-      }
-      for (; k < cnt; ++k) acc = acc + tile[k * 3 + tid];
+      acc = st_chain3(acc, tile, cnt, tid);
     }
     __syncthreads();
   }
