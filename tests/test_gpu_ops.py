@@ -429,7 +429,8 @@ def test_max_pool_points(P, b, p, ns, c):
 
 def test_deterministic_grads_long_lists_and_atomic_variants(P):
     """Heavily repeated targets (lists far longer than one wave: the 64-smallest-at-a-time path), a cloud with an
-    untouched row (gradient must be an exact 0), and the atomic variants (same value up to summation order)."""
+    untouched row (gradient must be an exact 0), and the atomic variants (same value up to summation order).
+    gather_point and three_interpolate on such lists, and their atomic variants: tests/test_gpu_grad_edges.py."""
     from pointasnl_amd import _hip
 
     rng = np.random.default_rng(3)
