@@ -837,6 +837,80 @@ int pasnl_cls_vote(int b, int c, const float* logits, const int* labels, double*
 int pasnl_cls_tally(int b, int bsize, int c, int num_votes, const int* labels, double* sums, long long* totals, long long* seen_class,
                     long long* correct_class, int* preds, double* loss, pasnl_stream_t stream);
 
+/* ---- ScanNet's training-time validation loops on the device (ScanNet/scannet_dataset.py (D) :31-64
+ * `ScannetDataset.__getitem__` and :92-129 `ScannetDatasetWholeScene.__getitem__`; ScanNet/train_scannet.py (T) :279-329
+ * `eval_one_epoch` and :333-420 `eval_whole_scene_one_epoch`; utils/provider.py (P) :8-24 `normalize_data` and :71-89
+ * `rotate_point_cloud_z`).  One scene at a time: xyz (n,3) f32 never moves, labels (n) i32 in [0,c); coordmin / coordmax
+ * (D:37-38, D:98-99) are the six device floats of pasnl_window_bounds.  The numpy RNG stream, the acceptance test of a try
+ * (D:55, two Python-float comparisons on three integers) and the carry-over of rows between scenes (T:357-382, over row
+ * counts only) stay on the host.  n <= 2^30; coordinates are finite. */
+
+/* The keys the voxel bitmap distinguishes (2^19): bitmap buffers hold 1 + capacity / 32 device words. */
+int pasnl_block_key_capacity(void);
+
+/* One try of the chopped-scene crop (D:41-55), counted in one pass over the scene.  The centre is read on the device:
+ * curcenter = xyz[centre], curmin = float64(curcenter) - [0.75, 0.75, .], curmax = float64(curcenter) + [0.75, 0.75, .],
+ * curmin[2] = float64(coordmin_z), curmax[2] = float64(coordmax_z).  A point is a member when its float32 coordinates,
+ * widened, are >= curmin - 0.2 and <= curmax + 0.2 on all three axes, compared in float64 exactly so (D:46); the mask of D:52
+ * is the same test with 0.01.  For the masked members the voxel key is the reference's float64 expression, operation for
+ * operation: v = ceil((p - curmin) / (curmax - curmin) * [31, 31, 62]), key = vx * 31.0 * 62.0 + vy * 62.0 + vz -- a key,
+ * not a cell triple: distinct triples that share a key count once, as under np.unique.  Keys are counted with a bitmap over
+ * [key_lo, key_lo + span) that the host sizes from the extents (a workgroup sets bits in LDS, OR-merges them into `bitmap`,
+ * and a last pass takes the popcount); span > pasnl_block_key_capacity() -> PASNL_EUNSUPPORTED.  hist:
+ * pasnl_window_hist_bytes(n, 2, 1) device bytes -- per chunk of 64 consecutive points the member count and the count of
+ * members with label > 0 (wave ballots), each scanned in place to the count in earlier chunks; the first row is the input
+ * of pasnl_block_fill.  -> out_stats (4) i32: m = len(cur_semantic_seg), np.sum(cur_semantic_seg > 0), len(np.unique(keys)),
+ * and a flag that is non-zero when a key fell outside the span or was NaN (the count is then not to be used).  A clear and
+ * three launches. */
+int pasnl_block_crop_stats(long n, const float* xyz, const int* labels, const float* bounds, long centre, long long key_lo, long span,
+                           int* hist, unsigned int* bitmap, int* out_stats, pasnl_stream_t stream);
+
+/* The whole-scene columns (D:105-113), counted.  Column w = i * ny + j (i < nx, j < ny, the reference's loop order) has
+ * curmin = float64(coordmin) + [i * 1.5, j * 1.5, 0] and curmax = float64(coordmin) + [(i + 1) * 1.5, (j + 1) * 1.5,
+ * float32(coordmax_z - coordmin_z)] -- the upper bound is NOT curmin + 1.5 as in pasnl_window_count, and rounds
+ * differently; membership is the 0.2-margin test of pasnl_block_crop_stats.  hist: pasnl_window_hist_bytes(n, nx, ny) device
+ * bytes, as in pasnl_window_count.  -> out_counts (nx*ny) i32, empty columns included.  nx, ny <= 64, else
+ * PASNL_EUNSUPPORTED.  Two launches. */
+int pasnl_block_grid_count(long n, const float* xyz, const float* bounds, int nx, int ny, int* hist, int* out_counts,
+                           pasnl_stream_t stream);
+
+/* The member lists (D:47-52, D:110-115): column w's members, in ascending scene index, go to out_idx[woff[w] ...] (woff
+ * (nx*ny) i32, -1: skip the column) and out_mask[...] is the inner-margin test -- 0.01 for the chopped column (centre >= 0,
+ * nx = ny = 1, hist from pasnl_block_crop_stats of the same centre), 0.001 for the grid (centre < 0, hist from
+ * pasnl_block_grid_count).  A member's rank is its chunk's scanned count plus the members among the lower lanes of its
+ * wave: deterministic, no arrival order.  cap: the length of out_idx / out_mask (nothing is written at or past it). */
+int pasnl_block_fill(long n, const float* xyz, const float* bounds, long centre, int nx, int ny, const int* hist, const int* woff, long cap,
+                     int* out_idx, unsigned char* out_mask, pasnl_stream_t stream);
+
+/* Rows (D:58-63, D:116-122): rowpos (rows,block_points) i32 holds, per row entry, woff[w] + the host's rng.choice(count_w,
+ * block_points) draw; entry e gets i = cat_idx[rowpos[e]], out_data[e] = xyz[i] | rgb[i] (3 + nfeat f32), out_label[e] =
+ * labels[i] and out_smpw[e] = float32(labelweights[labels[i]] * cat_mask[rowpos[e]]) (labelweights (c) f64; the float64
+ * product as the reference forms it, rounded as the float32 batch rounds it). */
+int pasnl_block_gather(int rows, int block_points, const int* rowpos, long cap, const int* cat_idx, const unsigned char* cat_mask, long n,
+                       const float* xyz, const float* rgb, int nfeat, const int* labels, int c, const double* labelweights,
+                       float* out_data, int* out_label, float* out_smpw, pasnl_stream_t stream);
+
+/* normalize_data (P:8-24), then optionally rotate_point_cloud_z (P:71-89), for rows blocks of src (rows,block_points,width)
+ * f32 into batch (rows,block_points,width) f32, one workgroup per block, in float64 as both loops hold the batch: centroid =
+ * per column ONE float64 sum down the rows (the chain of pasnl_window_noise) / float64(block_points), pc - centroid, m =
+ * max(sqrt((x*x + y*y) + z*z)), pc / m.  rot NULL: rounded to float32, the feed into the placeholder (T:384).  rot (rows,2)
+ * f64 = the host's cos and sin of each row's angle: [x y z] @ [[cos, sin, 0], [-sin, cos, 0], [0, 0, 1]] on the float64
+ * block, rounded to float32 (T:301-302; within one float32 ulp of numpy's product, whose dgemm fixes no summation order).
+ * Columns 3.. are copied. */
+int pasnl_block_normalize(int rows, int block_points, int width, const float* src, const double* rot, float* batch,
+                          pasnl_stream_t stream);
+
+/* The score of one batch (T:311-321, T:391-402): pred = np.argmax(logits, 2) over ALL c classes (the FIRST maximum, numpy's
+ * NaN rule); counters (2 + 4c) i64 += total_correct, total_seen, then per class seen, correct, iou_deno under smpw > 0 and
+ * the label histogram of every entry (T:316): integers, exact and order-free.  loss[1] = the batch's classify loss as
+ * tf.losses.sparse_softmax_cross_entropy(labels, logits, weights=smpw) gives it -- sum(w * ce) / count(w != 0), 0 when
+ * that count is 0 (a float32 log-sum-exp per entry, float64 partial sums per workgroup added in workgroup order: no float
+ * atomics; compared under a tolerance, never by bits) -- and loss[0] += loss[1].  workspace:
+ * pasnl_block_score_workspace_bytes() device bytes.  c <= 256, else PASNL_EUNSUPPORTED.  Two launches. */
+size_t pasnl_block_score_workspace_bytes(void);
+int pasnl_block_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw, long long* counters,
+                      double* loss, void* workspace, pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

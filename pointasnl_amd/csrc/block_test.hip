@@ -1,0 +1,444 @@
+// ScanNet's two training-time validation loops around the forward, on the device: reference ScanNet/scannet_dataset.py (D)
+// :31-64 `ScannetDataset.__getitem__` (a 1.5 m column round a drawn centre, rejected unless 70 % of it is labelled and 2 % of a
+// 31x31x62 voxel grid is occupied, resampled to block_points rows) and :92-129 `ScannetDatasetWholeScene.__getitem__` (every
+// non-empty column of a non-overlapping 1.5 m grid, resampled likewise), ScanNet/train_scannet.py (T) :279-329
+// `eval_one_epoch` and :333-420 `eval_whole_scene_one_epoch` (argmax over ALL classes, counters under smpw > 0, the weighted
+// cross-entropy) and utils/provider.py (P) :8-24 `normalize_data`, :71-89 `rotate_point_cloud_z`.  The sixth sibling of
+// scan_test.hip, scene_test.hip, window_test.hip, kitti_window_test.hip and modelnet_test.hip.  Everything that has to equal
+// numpy is done in numpy's dtypes and order (the library builds with -ffp-contract=off); the exactness contract is stated in
+// include/pasnl.h per entry point and restated on the host in tests/block_flow_ref.py.
+//
+// What stays on the host: the numpy RNG stream (the centre of every try, the resampling choices, the rotation angles), the
+// acceptance test of a try (two Python-float comparisons on three integers) and the carry-over of rows between scenes.
+//   chopped: per try pasnl_block_crop_stats -> [four integers down]; then [choices up] -> pasnl_block_fill -> pasnl_block_gather
+//   whole:   pasnl_block_grid_count -> [nx*ny counts down; choices up] -> pasnl_block_fill -> pasnl_block_gather
+//   per batch, with no synchronisation: pasnl_block_normalize -> forward -> pasnl_block_score
+#include <math.h>
+#include "common.hpp"
+#include "test_loop.hpp"
+#include "window_scan.hpp"
+
+namespace pasnl {
+
+constexpr int BT_WAVES = 4;            // chunks (of 64 consecutive points, one wave each) in flight per workgroup
+constexpr int BT_KEYS = 1 << 19;       // voxel keys the bitmap distinguishes: 64 KiB of LDS per workgroup
+constexpr int BT_MAX_GROUPS = 1024;    // workgroups of the statistics pass (each clears and merges one LDS bitmap)
+constexpr int BT_AXIS_MAX = 64;        // columns per axis: a point's memberships along an axis are one 64-bit mask
+constexpr int BT_CLASS_MAX = 256;      // classes whose counters a workgroup keeps in LDS
+constexpr int BT_SCORE_GROUPS = 256;   // workgroups of the score pass == partial loss sums the last pass adds in order
+
+// ---- the chopped column (D:41-46, 52): float64 bounds from the float32 centre and the float32 z extent of the scene
+struct CropBox {
+  double lo[3], hi[3];
+};
+
+__device__ __forceinline__ CropBox crop_box(const float* __restrict__ centre, const float* __restrict__ b) {
+  CropBox box;
+  box.lo[0] = (double)centre[0] - 0.75;  // curcenter - [0.75, 0.75, 1.5]: float32 array - list -> float64
+  box.hi[0] = (double)centre[0] + 0.75;
+  box.lo[1] = (double)centre[1] - 0.75;
+  box.hi[1] = (double)centre[1] + 0.75;
+  box.lo[2] = (double)b[2];  // curmin[2] = coordmin[2]; curmax[2] = coordmax[2]
+  box.hi[2] = (double)b[5];
+  return box;
+}
+
+__device__ __forceinline__ bool crop_inside(const CropBox& box, const double* p, double margin) {
+  bool in = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) in = in && p[a] >= box.lo[a] - margin && p[a] <= box.hi[a] + margin;
+  return in;
+}
+
+// Pass 1 of a try, one wave per chunk: hist[c] = members (0.2 margin), hist[nchunks + c] = members with label > 0 (two
+// ballots, no atomics), and the voxel key of every member inside the 0.01 margin set in the workgroup's LDS bitmap, which is
+// OR-merged into bitmap[1 + word] at the end; bitmap[0] flags a key outside [key_lo, key_lo + 32 * words) or a NaN key.
+__global__ __launch_bounds__(64 * BT_WAVES) void block_crop_stats_kernel(long n, const float* __restrict__ xyz, const int* __restrict__ labels,
+                                                                         const float* __restrict__ bounds, long centre, double key_lo,
+                                                                         int words, long nchunks, int* __restrict__ hist,
+                                                                         unsigned* __restrict__ bitmap) {
+  extern __shared__ unsigned bits[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int k = tid; k < words; k += 64 * BT_WAVES) bits[k] = 0u;
+  __syncthreads();
+  const CropBox box = crop_box(xyz + centre * 3, bounds);
+  const double span = (double)words * 32.0;
+  for (long c = (long)blockIdx.x * BT_WAVES + (tid >> 6); c < nchunks; c += (long)gridDim.x * BT_WAVES) {  // (wave-uniform)
+    const long p = c * 64 + lane;
+    bool in20 = false, in1 = false, lab = false;
+    double q[3] = {0.0, 0.0, 0.0};
+    if (p < n) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) q[a] = (double)xyz[p * 3 + a];
+      in20 = crop_inside(box, q, 0.2);
+      in1 = in20 && crop_inside(box, q, 0.01);
+      lab = in20 && labels[p] > 0;
+    }
+    const unsigned long long b20 = __ballot(in20), bl = __ballot(lab);
+    if (lane == 0) {
+      hist[c] = __popcll(b20);
+      hist[nchunks + c] = __popcll(bl);
+    }
+    if (in1) {  // np.ceil((p - curmin) / (curmax - curmin) * [31.0, 31.0, 62.0]); vx * 31.0 * 62.0 + vy * 62.0 + vz
+      const double vx = ceil(((q[0] - box.lo[0]) / (box.hi[0] - box.lo[0])) * 31.0);
+      const double vy = ceil(((q[1] - box.lo[1]) / (box.hi[1] - box.lo[1])) * 31.0);
+      const double vz = ceil(((q[2] - box.lo[2]) / (box.hi[2] - box.lo[2])) * 62.0);
+      const double rel = (((vx * 31.0) * 62.0 + vy * 62.0) + vz) - key_lo;  // integers far below 2^53: exact
+      if (rel >= 0.0 && rel < span) {
+        const unsigned r = (unsigned)rel;
+        atomicOr(&bits[r >> 5], 1u << (r & 31u));
+      } else {
+        atomicOr(&bitmap[0], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < words; k += 64 * BT_WAVES) {
+    const unsigned v = bits[k];
+    if (v) atomicOr(&bitmap[1 + k], v);
+  }
+}
+
+// Pass 3 of a try (pass 2 is window_scan_kernel over the two histograms): len(np.unique(keys)) = the bitmap's popcount
+__global__ __launch_bounds__(256) void block_unique_kernel(int words, const unsigned* __restrict__ bitmap, int* __restrict__ stats) {
+  __shared__ int sh[4];
+  int cnt = 0;
+  for (int k = threadIdx.x; k < words; k += 256) cnt += __popc(bitmap[1 + k]);
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    stats[2] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    stats[3] = (int)bitmap[0];
+  }
+}
+
+// ---- membership of a point in the columns, as masks (the form of window_test.hip's WinMember)
+struct BlockMember {
+  unsigned long long x20, y20, x1, y1;
+  bool z20, z1;
+};
+
+// the whole-scene grid (D:107-109, 115): curmin = float64(coordmin) + i * 1.5, curmax = float64(coordmin) + (i + 1) * 1.5 --
+// NOT curmin + 1.5, which rounds differently; i * 1.5 and (i + 1) * 1.5 are exact
+__device__ __forceinline__ void grid_axis_masks(double p, double origin, int count, unsigned long long& m20, unsigned long long& m1) {
+  m20 = 0ull;
+  m1 = 0ull;
+  for (int i = 0; i < count; ++i) {
+    const double curmin = origin + (double)i * 1.5;
+    const double curmax = origin + (double)(i + 1) * 1.5;
+    if (p >= curmin - 0.2 && p <= curmax + 0.2) m20 |= 1ull << i;
+    if (p >= curmin - 0.001 && p <= curmax + 0.001) m1 |= 1ull << i;
+  }
+}
+
+__device__ __forceinline__ BlockMember grid_member(const float* __restrict__ p, const float* __restrict__ b, int nx, int ny) {
+  BlockMember m;
+  grid_axis_masks((double)p[0], (double)b[0], nx, m.x20, m.x1);
+  grid_axis_masks((double)p[1], (double)b[1], ny, m.y20, m.y1);
+  const double pz = (double)p[2];
+  const double zmin = (double)b[2] + 0.0;
+  const double zmax = (double)b[2] + (double)(b[5] - b[2]);  // coordmin + [.., .., coordmax[2] - coordmin[2]]: a float32 difference
+  m.z20 = pz >= zmin - 0.2 && pz <= zmax + 0.2;
+  m.z1 = pz >= zmin - 0.001 && pz <= zmax + 0.001;
+  return m;
+}
+
+// the chopped column as the single "window" 0 of the same form (the 0.01 margin in the *1 fields)
+__device__ __forceinline__ BlockMember crop_member(const float* __restrict__ p, const CropBox& box) {
+  const double q[3] = {(double)p[0], (double)p[1], (double)p[2]};
+  BlockMember m = {0ull, 0ull, 0ull, 0ull, false, false};
+  m.x20 = q[0] >= box.lo[0] - 0.2 && q[0] <= box.hi[0] + 0.2;
+  m.y20 = q[1] >= box.lo[1] - 0.2 && q[1] <= box.hi[1] + 0.2;
+  m.z20 = q[2] >= box.lo[2] - 0.2 && q[2] <= box.hi[2] + 0.2;
+  m.x1 = q[0] >= box.lo[0] - 0.01 && q[0] <= box.hi[0] + 0.01;
+  m.y1 = q[1] >= box.lo[1] - 0.01 && q[1] <= box.hi[1] + 0.01;
+  m.z1 = q[2] >= box.lo[2] - 0.01 && q[2] <= box.hi[2] + 0.01;
+  return m;
+}
+
+// whole scene, pass 1: hist[w][chunk] = members of column w among the chunk's 64 points (a ballot: no atomics at all)
+__global__ __launch_bounds__(64 * BT_WAVES) void block_grid_count_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
+                                                                         int nx, int ny, long nchunks, int* __restrict__ hist) {
+  const int lane = threadIdx.x & 63;
+  const long c = (long)blockIdx.x * BT_WAVES + (threadIdx.x >> 6);
+  if (c >= nchunks) return;  // whole waves leave
+  const long p = c * 64 + lane;
+  BlockMember m = {0ull, 0ull, 0ull, 0ull, false, false};
+  if (p < n) m = grid_member(xyz + p * 3, bounds, nx, ny);
+  for (int i = 0; i < nx; ++i) {
+    const bool fx = m.z20 && ((m.x20 >> i) & 1ull);
+    for (int j = 0; j < ny; ++j) {
+      const unsigned long long ballot = __ballot(fx && ((m.y20 >> j) & 1ull));
+      if (lane == 0) hist[(size_t)(i * ny + j) * nchunks + c] = __popcll(ballot);
+    }
+  }
+}
+
+// both loops, the last pass: a member's place is woff[w] + (members in earlier chunks) + (members among the lower lanes):
+// ascending scene index.  centre >= 0: the chopped column round that point (nx = ny = 1); centre < 0: the grid.
+__global__ __launch_bounds__(64 * BT_WAVES) void block_fill_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
+                                                                   long centre, int nx, int ny, long nchunks, const int* __restrict__ hist,
+                                                                   const int* __restrict__ woff, long cap, int* __restrict__ out_idx,
+                                                                   unsigned char* __restrict__ out_mask) {
+  const int lane = threadIdx.x & 63;
+  const long c = (long)blockIdx.x * BT_WAVES + (threadIdx.x >> 6);
+  if (c >= nchunks) return;
+  const long p = c * 64 + lane;
+  BlockMember m = {0ull, 0ull, 0ull, 0ull, false, false};
+  if (p < n) m = centre >= 0 ? crop_member(xyz + p * 3, crop_box(xyz + centre * 3, bounds)) : grid_member(xyz + p * 3, bounds, nx, ny);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int i = 0; i < nx; ++i) {
+    const bool fx = m.z20 && ((m.x20 >> i) & 1ull);
+    for (int j = 0; j < ny; ++j) {
+      const bool in = fx && ((m.y20 >> j) & 1ull);
+      const unsigned long long ballot = __ballot(in);
+      const int w = i * ny + j;
+      if (in) {
+        const int off = woff[w];
+        const long pos = (long)off + hist[(size_t)w * nchunks + c] + __popcll(ballot & below);
+        if (off >= 0 && pos < cap) {  // (the host sizes the lists from the counts: always taken for a listed column)
+          out_idx[pos] = (int)p;
+          out_mask[pos] = (m.z1 && ((m.x1 >> i) & 1ull) && ((m.y1 >> j) & 1ull)) ? 1 : 0;
+        }
+      }
+    }
+  }
+}
+
+// ---- rows (D:58-63, D:116-122): one thread per row entry
+__global__ __launch_bounds__(256) void block_gather_kernel(long entries, const int* __restrict__ rowpos, long cap, const int* __restrict__ cat_idx,
+                                                           const unsigned char* __restrict__ cat_mask, long n, const float* __restrict__ xyz,
+                                                           const float* __restrict__ rgb, int nfeat, const int* __restrict__ labels, int c,
+                                                           const double* __restrict__ labelweights, float* __restrict__ out_data,
+                                                           int* __restrict__ out_label, float* __restrict__ out_smpw) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= entries) return;
+  const int width = 3 + nfeat;
+  float* row = out_data + (size_t)e * width;
+  const long pos = rowpos[e];
+  const long i = pos >= 0 && pos < cap ? (long)cat_idx[pos] : -1;
+  const int l = i >= 0 && i < n ? labels[i] : -1;
+  if (l < 0 || l >= c) {  // (a position outside the lists is never drawn, a label outside the table never stored)
+    for (int f = 0; f < width; ++f) row[f] = 0.0f;
+    out_label[e] = 0;
+    out_smpw[e] = 0.0f;
+    return;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) row[a] = xyz[i * 3 + a];
+  for (int f = 0; f < nfeat; ++f) row[3 + f] = rgb[i * nfeat + f];
+  out_label[e] = l;
+  out_smpw[e] = (float)(labelweights[l] * (cat_mask[pos] ? 1.0 : 0.0));  // float64 weight *= mask, stored to a float32 batch
+}
+
+// ---- P:8-24 (+ P:71-89): one block of the batch per workgroup, in float64 as both loops hold the batch
+constexpr int BN_TILE = 2048;  // rows per staged tile: 48 KiB of LDS
+
+__global__ __launch_bounds__(ST_THREADS) void block_normalize_kernel(int npoint, int width, const float* __restrict__ src,
+                                                                     const double* __restrict__ rot, float* __restrict__ batch) {
+  __shared__ double tile[BN_TILE * 3];
+  __shared__ double cen[3], shm[ST_WAVES];
+  const int tid = threadIdx.x;
+  const float* __restrict__ p = src + (size_t)blockIdx.x * npoint * width;
+  float* __restrict__ out = batch + (size_t)blockIdx.x * npoint * width;
+  double acc = -0.0;
+  for (int base = 0; base < npoint; base += BN_TILE) {
+    const int cnt = npoint - base < BN_TILE ? npoint - base : BN_TILE;
+    for (int k = tid; k < cnt * 3; k += ST_THREADS) tile[k] = (double)p[(size_t)(base + k / 3) * width + k % 3];
+    __syncthreads();
+    if (tid < 3) acc = st_chain3(acc, tile, cnt, tid);
+    __syncthreads();
+  }
+  if (tid < 3) cen[tid] = acc / (double)npoint;
+  __syncthreads();
+  double m = -__builtin_inf();
+  for (int i = tid; i < npoint; i += ST_THREADS) {
+    const double x = (double)p[(size_t)i * width] - cen[0], y = (double)p[(size_t)i * width + 1] - cen[1],
+                 z = (double)p[(size_t)i * width + 2] - cen[2];
+    m = nan_max(m, sqrt((x * x + y * y) + z * z));
+  }
+  for (int o = 32; o > 0; o >>= 1) m = nan_max(m, __shfl_xor(m, o, 64));
+  if ((tid & 63) == 0) shm[tid >> 6] = m;
+  __syncthreads();
+  m = shm[0];
+#pragma unroll
+  for (int w = 1; w < ST_WAVES; ++w) m = nan_max(m, shm[w]);
+  const bool turn = rot != nullptr;
+  const double cosval = turn ? rot[blockIdx.x * 2] : 1.0, sinval = turn ? rot[blockIdx.x * 2 + 1] : 0.0;
+  for (int i = tid; i < npoint; i += ST_THREADS) {
+    const float* r = p + (size_t)i * width;
+    float* o = out + (size_t)i * width;
+    const double x = ((double)r[0] - cen[0]) / m, y = ((double)r[1] - cen[1]) / m, z = ((double)r[2] - cen[2]) / m;
+    if (turn) {  // [x y z] @ [[cos, sin, 0], [-sin, cos, 0], [0, 0, 1]] in float64, stored as float32
+      o[0] = (float)(x * cosval + y * -sinval);
+      o[1] = (float)(x * sinval + y * cosval);
+    } else {
+      o[0] = (float)x;  // the feed into a float32 placeholder
+      o[1] = (float)y;
+    }
+    o[2] = (float)z;
+    for (int f = 3; f < width; ++f) o[f] = r[f];
+  }
+}
+
+// ---- T:311-321, T:391-402: the counters (integers: exact and order-free) and the batch's weighted cross-entropy
+// counters (2 + 4c) i64: total_correct, total_seen, then seen[c], correct[c], iou_deno[c], label histogram[c]
+__global__ __launch_bounds__(256) void block_score_kernel(long entries, int c, const float* __restrict__ logits, const int* __restrict__ labels,
+                                                          const float* __restrict__ smpw, long long* __restrict__ counters,
+                                                          double* __restrict__ part_sum, long long* __restrict__ part_cnt) {
+  __shared__ int cnt[2 + 4 * BT_CLASS_MAX];
+  __shared__ double shs[4];
+  __shared__ int shn[4];
+  const int tid = threadIdx.x, ncnt = 2 + 4 * c;
+  for (int k = tid; k < ncnt; k += 256) cnt[k] = 0;
+  __syncthreads();
+  double sum = 0.0;
+  int nz = 0;
+  for (long e = (long)blockIdx.x * 256 + tid; e < entries; e += (long)gridDim.x * 256) {
+    const float* row = logits + (size_t)e * c;
+    int a = 0;
+    float best = row[0];
+    bool nan = best != best;
+    for (int q = 1; q < c && !nan; ++q) {  // np.argmax(pred_val, 2): the first maximum, the first NaN
+      const float v = row[q];
+      if (v > best || v != v) { best = v; a = q; nan = v != v; }
+    }
+    const int l = labels[e];
+    const float w = smpw[e];
+    if (l < 0 || l >= c) continue;
+    atomicAdd(&cnt[2 + 3 * c + l], 1);  // np.histogram(batch_label, range(c + 1)): every entry
+    if (w > 0.0f) {
+      atomicAdd(&cnt[2 + l], 1);
+      atomicAdd(&cnt[2 + 2 * c + l], 1);                // (pred == l) | (label == l), l = the label
+      if (a == l) {
+        atomicAdd(&cnt[2 + c + l], 1);
+        if (l > 0) atomicAdd(&cnt[0], 1);
+      } else {
+        atomicAdd(&cnt[2 + 2 * c + a], 1);              // ..., l = the prediction
+      }
+      if (l > 0) atomicAdd(&cnt[1], 1);
+    }
+    if (w != 0.0f) {  // tf.losses.sparse_softmax_cross_entropy(weights=smpw): sum(w * ce) / count(w != 0)
+      float mx = row[0];
+      for (int q = 1; q < c; ++q) mx = row[q] > mx ? row[q] : mx;
+      float s = 0.0f;
+      for (int q = 0; q < c; ++q) s += expf(row[q] - mx);
+      sum += (double)w * (double)((logf(s) + mx) - row[l]);
+      nz += 1;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, 64);
+    nz += __shfl_xor(nz, o, 64);
+  }
+  if ((tid & 63) == 0) { shs[tid >> 6] = sum; shn[tid >> 6] = nz; }
+  __syncthreads();
+  for (int k = tid; k < ncnt; k += 256)
+    if (cnt[k]) atomicAdd((unsigned long long*)&counters[k], (unsigned long long)cnt[k]);
+  if (tid == 0) {
+    part_sum[blockIdx.x] = ((shs[0] + shs[1]) + shs[2]) + shs[3];
+    part_cnt[blockIdx.x] = ((shn[0] + shn[1]) + shn[2]) + shn[3];
+  }
+}
+
+// the partial sums in workgroup order: loss[1] = the batch's classify loss, loss[0] += it
+__global__ __launch_bounds__(64) void block_loss_kernel(int groups, const double* __restrict__ part_sum, const long long* __restrict__ part_cnt,
+                                                        double* __restrict__ loss) {
+  if (threadIdx.x != 0) return;
+  double sum = 0.0;
+  long long nz = 0;
+  for (int g = 0; g < groups; ++g) { sum += part_sum[g]; nz += part_cnt[g]; }
+  const double v = nz > 0 ? sum / (double)nz : 0.0;
+  loss[1] = v;
+  loss[0] += v;
+}
+
+}  // namespace pasnl
+
+using namespace pasnl;
+
+extern "C" int pasnl_block_key_capacity(void) { return BT_KEYS; }
+
+extern "C" int pasnl_block_crop_stats(long n, const float* xyz, const int* labels, const float* bounds, long centre, long long key_lo,
+                                      long span, int* hist, unsigned int* bitmap, int* out_stats, pasnl_stream_t stream) {
+  PASNL_REQUIRE(n > 0 && n <= (1L << 30) && centre >= 0 && centre < n && span > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(span <= BT_KEYS, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(xyz && labels && bounds && hist && bitmap && out_stats, PASNL_ENULL);
+  hipStream_t s = pasnl_hip_stream(stream);
+  const long nchunks = wt_chunks(n);
+  const int words = (int)((span + 31) / 32);
+  const unsigned groups = wt_blocks(nchunks, BT_WAVES) < (unsigned)BT_MAX_GROUPS ? wt_blocks(nchunks, BT_WAVES) : (unsigned)BT_MAX_GROUPS;
+  if (hipMemsetAsync(bitmap, 0, (size_t)(1 + words) * sizeof(unsigned), s) != hipSuccess) return PASNL_ELAUNCH;
+  const int rc = launch(block_crop_stats_kernel, dim3(groups), dim3(64 * BT_WAVES), (size_t)words * sizeof(unsigned), s, n, xyz, labels, bounds,
+                        centre, (double)key_lo, words, nchunks, hist, bitmap);
+  if (rc != PASNL_OK) return rc;
+  hipLaunchKernelGGL(window_scan_kernel, dim3(2), dim3(256), 0, s, nchunks, hist, out_stats);
+  hipLaunchKernelGGL(block_unique_kernel, dim3(1), dim3(256), 0, s, words, bitmap, out_stats);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_block_grid_count(long n, const float* xyz, const float* bounds, int nx, int ny, int* hist, int* out_counts,
+                                      pasnl_stream_t stream) {
+  PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0, PASNL_EINVAL);
+  PASNL_REQUIRE(nx <= BT_AXIS_MAX && ny <= BT_AXIS_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(xyz && bounds && hist && out_counts, PASNL_ENULL);
+  hipStream_t s = pasnl_hip_stream(stream);
+  const long nchunks = wt_chunks(n);
+  hipLaunchKernelGGL(block_grid_count_kernel, dim3(wt_blocks(nchunks, BT_WAVES)), dim3(64 * BT_WAVES), 0, s, n, xyz, bounds, nx, ny, nchunks,
+                     hist);
+  hipLaunchKernelGGL(window_scan_kernel, dim3(nx * ny), dim3(256), 0, s, nchunks, hist, out_counts);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_block_fill(long n, const float* xyz, const float* bounds, long centre, int nx, int ny, const int* hist, const int* woff,
+                                long cap, int* out_idx, unsigned char* out_mask, pasnl_stream_t stream) {
+  PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0 && cap > 0 && centre < n && (centre < 0 || (nx == 1 && ny == 1)),
+                PASNL_EINVAL);
+  PASNL_REQUIRE(nx <= BT_AXIS_MAX && ny <= BT_AXIS_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(xyz && bounds && hist && woff && out_idx && out_mask, PASNL_ENULL);
+  const long nchunks = wt_chunks(n);
+  hipLaunchKernelGGL(block_fill_kernel, dim3(wt_blocks(nchunks, BT_WAVES)), dim3(64 * BT_WAVES), 0, pasnl_hip_stream(stream), n, xyz, bounds,
+                     centre, nx, ny, nchunks, hist, woff, cap, out_idx, out_mask);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_block_gather(int rows, int block_points, const int* rowpos, long cap, const int* cat_idx, const unsigned char* cat_mask,
+                                  long n, const float* xyz, const float* rgb, int nfeat, const int* labels, int c, const double* labelweights,
+                                  float* out_data, int* out_label, float* out_smpw, pasnl_stream_t stream) {
+  PASNL_REQUIRE(rows >= 0 && block_points > 0 && nfeat >= 0 && n > 0 && cap > 0 && c >= 1, PASNL_EINVAL);
+  if (rows == 0) return PASNL_OK;
+  PASNL_REQUIRE(rowpos && cat_idx && cat_mask && xyz && labels && labelweights && out_data && out_label && out_smpw && (nfeat == 0 || rgb),
+                PASNL_ENULL);
+  const long entries = (long)rows * block_points;
+  hipLaunchKernelGGL(block_gather_kernel, dim3(wt_blocks(entries, 256)), dim3(256), 0, pasnl_hip_stream(stream), entries, rowpos, cap, cat_idx,
+                     cat_mask, n, xyz, rgb, nfeat, labels, c, labelweights, out_data, out_label, out_smpw);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_block_normalize(int rows, int block_points, int width, const float* src, const double* rot, float* batch,
+                                     pasnl_stream_t stream) {
+  PASNL_REQUIRE(rows >= 0 && block_points > 0 && width >= 3, PASNL_EINVAL);
+  if (rows == 0) return PASNL_OK;
+  PASNL_REQUIRE(src && batch, PASNL_ENULL);
+  hipLaunchKernelGGL(block_normalize_kernel, dim3(rows), dim3(ST_THREADS), 0, pasnl_hip_stream(stream), block_points, width, src, rot, batch);
+  return pasnl_launch_status();
+}
+
+extern "C" size_t pasnl_block_score_workspace_bytes(void) { return (size_t)BT_SCORE_GROUPS * (sizeof(double) + sizeof(long long)); }
+
+extern "C" int pasnl_block_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw,
+                                 long long* counters, double* loss, void* workspace, pasnl_stream_t stream) {
+  PASNL_REQUIRE(rows >= 0 && block_points > 0 && c >= 1, PASNL_EINVAL);
+  PASNL_REQUIRE(c <= BT_CLASS_MAX, PASNL_EUNSUPPORTED);
+  if (rows == 0) return PASNL_OK;
+  PASNL_REQUIRE(logits && labels && smpw && counters && loss && workspace, PASNL_ENULL);
+  hipStream_t s = pasnl_hip_stream(stream);
+  const long entries = (long)rows * block_points;
+  const int groups = wt_blocks(entries, 256) < (unsigned)BT_SCORE_GROUPS ? (int)wt_blocks(entries, 256) : BT_SCORE_GROUPS;
+  double* part_sum = static_cast<double*>(workspace);
+  long long* part_cnt = reinterpret_cast<long long*>(part_sum + BT_SCORE_GROUPS);
+  hipLaunchKernelGGL(block_score_kernel, dim3(groups), dim3(256), 0, s, entries, c, logits, labels, smpw, counters, part_sum, part_cnt);
+  hipLaunchKernelGGL(block_loss_kernel, dim3(1), dim3(64), 0, s, groups, part_sum, part_cnt, loss);
+  return pasnl_launch_status();
+}
