@@ -911,6 +911,64 @@ size_t pasnl_block_score_workspace_bytes(void);
 int pasnl_block_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw, long long* counters,
                       double* loss, void* workspace, pasnl_stream_t stream);
 
+/* ---- SemanticKITTI's training-time validation loops on the device (SemanticKITTI/semantic_kitti_dataset.py (D) :68-109
+ * `SemanticKittiDataset.__getitem__` and :164-211 `SemanticKittiDataset_whole.__getitem__`; SemanticKITTI/train_semantic_kitti.py
+ * (T) :267-328 `eval_one_epoch` and :331-418 `eval_whole_scene_one_epoch`; utils/provider.py (P) :71-89
+ * `rotate_point_cloud_z`).  One scan at a time: xyz (n,3) f32 never moves, labels (n) i32 in [0,c), remission (n) f32 is
+ * optional; coordmin / coordmax (D:78-79, D:174-175) are the six device floats of pasnl_window_bounds, and a batch is scored
+ * by pasnl_block_score.  Every comparison is the reference's own: the float32 coordinate widened to float64 against a float64
+ * bound; no index is derived from a division.  The numpy RNG stream, the acceptance test of a try (D:97) and the carry-over of
+ * rows between scans (T:354-379, over row counts only) stay on the host.  n <= 2^30; coordinates are finite. */
+
+/* One try of the chopped-scan crop (D:82-97), counted in one pass over the scan.  The centre is read on the device:
+ * curcenter = xyz[centre], curmin = float64(curcenter) - [half, half, .], curmax = float64(curcenter) + [half, half, .] with
+ * half = the host's block_size / 2, curmin[2] = float64(coordmin_z), curmax[2] = float64(coordmax_z).  A point is a member
+ * when it is >= curmin - 0.2 and <= curmax + 0.2 on all three axes (D:87).  hist: pasnl_window_hist_bytes(n, 2, 1) device
+ * bytes -- per chunk of 64 consecutive points the member count and the count of members with label > 0 (wave ballots), each
+ * scanned in place to the count in earlier chunks; the first row is the input of pasnl_kblock_fill.  -> out_stats (2) i32:
+ * len(cur_semantic_seg) and np.sum(cur_semantic_seg > 0).  Two launches. */
+int pasnl_kblock_crop_stats(long n, const float* xyz, const int* labels, const float* bounds, long centre, double half, int* hist,
+                            int* out_stats, pasnl_stream_t stream);
+
+/* The whole-scan columns (D:182-192), counted.  Column w = i * ny + j (i < nx, j < ny, the reference's loop order) has curmin
+ * = float64(coordmin) + [i * block, j * block, 0] and curmax = float64(coordmin) + [(i + 1) * block, (j + 1) * block,
+ * float64(float32(coordmax_z - coordmin_z))] -- the upper bound is NOT curmin + block; membership is the 0.2-margin test of
+ * pasnl_kblock_crop_stats.  hist: pasnl_kwindow_hist_bytes(n, nx, ny) device bytes, laid out as there -- cleared, then per
+ * column and chunk the member count (a wave stores only for the columns inside the rectangle of its points' ranges; both
+ * bounds are monotone in i, so an axis's columns for a point are one range), then scanned in place per column.  ->
+ * out_counts (nx*ny) i32, empty columns included.  No limit per axis: nx * ny <= INT_MAX, else PASNL_EUNSUPPORTED.  Cost:
+ * every point tests every column of both axes, nx + ny float64 comparisons per point here and again in pasnl_kblock_fill --
+ * nothing at the 10 to 100 columns per axis of a lidar scan, linear in them beyond.  A clear and two launches. */
+int pasnl_kblock_grid_count(long n, const float* xyz, const float* bounds, int nx, int ny, double block, int* hist, int* out_counts,
+                            pasnl_stream_t stream);
+
+/* The member lists (D:87-95, D:186-193): column w's members, in ascending scan index, go to out_idx[woff[w] ...] (woff
+ * (nx*ny) i32, -1: skip the column) and out_mask[...] is the same test with `padding` in place of 0.2 (D:95, D:193).  centre
+ * >= 0: the chopped column round that point (nx = ny = 1, hist from pasnl_kblock_crop_stats of the same centre and half);
+ * centre < 0: the grid (hist from pasnl_kblock_grid_count of the same nx, ny and block).  A member's rank is its chunk's
+ * scanned count plus the members among the lower lanes of its wave: deterministic, no atomics and no arrival order.  cap: the
+ * length of out_idx / out_mask (nothing is written at or past it). */
+int pasnl_kblock_fill(long n, const float* xyz, const float* bounds, long centre, double half, int nx, int ny, double block, double padding,
+                      const int* hist, const int* woff, long cap, int* out_idx, unsigned char* out_mask, pasnl_stream_t stream);
+
+/* Rows (D:100-107, D:195-203): rowpos (rows,block_points) i32 holds, per row entry, woff[w] + the host's rng.choice(count_w,
+ * block_points) draw and rowbase (rows) i32 the row's woff[w], so the draw itself is rowpos[e] - rowbase[row].  Entry e gets
+ * i = cat_idx[rowpos[e]], seg = labels[i], out_data[e] = xyz[i] followed by one remission when nfeat == 1 (nfeat is 0 or 1),
+ * out_label[e] = seg.  lut (c) f32, c <= 256 else PASNL_EUNSUPPORTED.  quirks != 0 reproduces the reference: out_smpw[e] =
+ * float32(lut[labels[seg]]) * float32(mask) -- label_weights = lut[label] is a per-point array that D:104 indexes by label
+ * value, so the caller guarantees n > max(label) -- and the remission is remission[rowpos[e] - rowbase[row]], that of scan
+ * point number `draw` (D:107 indexes the scan's remissions by the raw draw).  quirks == 0 is the evident intent: out_smpw[e]
+ * = lut[seg] * mask and remission[i]. */
+int pasnl_kblock_gather(int rows, int block_points, const int* rowpos, const int* rowbase, long cap, const int* cat_idx,
+                        const unsigned char* cat_mask, long n, const float* xyz, const float* remission, int nfeat, const int* labels,
+                        int c, const float* lut, int quirks, float* out_data, int* out_label, float* out_smpw, pasnl_stream_t stream);
+
+/* rotate_point_cloud_z (P:71-89) as T:290 applies it to the float64 batch, for rows blocks of src (rows,block_points,width)
+ * f32 into batch: [x y] -> [x * cos - y * sin, x * sin + y * cos] in float64 from the float32 row, rounded to float32 (within
+ * one float32 ulp of numpy's product, whose dgemm fixes no summation order); columns 2.. are copied.  rot (rows,2) f64 = the
+ * host's cos and sin of each row's angle.  src == batch is allowed.  There is no normalize_data in these loops. */
+int pasnl_kblock_rotate(int rows, int block_points, int width, const float* src, const double* rot, float* batch, pasnl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

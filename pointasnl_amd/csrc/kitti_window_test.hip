@@ -37,10 +37,6 @@ __device__ __forceinline__ void axis_range(double p, double origin, int count, d
   }
 }
 
-struct KWinMember {
-  int xlo, xhi, ylo, yhi;  // an empty range on either axis, or z outside: xhi < xlo
-};
-
 __device__ __forceinline__ KWinMember kwin_member(const float* __restrict__ p, const float* __restrict__ b, int nx, int ny, double block,
                                                   double stride) {
   KWinMember m;
@@ -51,22 +47,6 @@ __device__ __forceinline__ KWinMember kwin_member(const float* __restrict__ p, c
   const double zmax = zmin + (double)(b[5] - b[2]);  // float64(float32(coordmax_z - coordmin_z))
   const bool z = pz >= zmin - 0.2 && pz <= zmax + 0.2;
   if (!z || m.yhi < m.ylo || m.xhi < m.xlo) m = {nx, -1, ny, -1};
-  return m;
-}
-
-// the rectangle of windows that holds every membership of the wave's 64 points (empty: xhi < xlo): uniform over the wave
-__device__ __forceinline__ KWinMember wave_rect(KWinMember m) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const int a = __shfl_xor(m.xlo, o, 64), b = __shfl_xor(m.xhi, o, 64), c = __shfl_xor(m.ylo, o, 64), d = __shfl_xor(m.yhi, o, 64);
-    m.xlo = a < m.xlo ? a : m.xlo;
-    m.xhi = b > m.xhi ? b : m.xhi;
-    m.ylo = c < m.ylo ? c : m.ylo;
-    m.yhi = d > m.yhi ? d : m.yhi;
-  }
-  m.xlo = __builtin_amdgcn_readfirstlane(m.xlo);  // every lane holds the same four values: the loops over them are scalar
-  m.xhi = __builtin_amdgcn_readfirstlane(m.xhi);
-  m.ylo = __builtin_amdgcn_readfirstlane(m.ylo);
-  m.yhi = __builtin_amdgcn_readfirstlane(m.yhi);
   return m;
 }
 

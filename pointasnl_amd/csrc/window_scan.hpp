@@ -1,5 +1,6 @@
 // What the two sliding-window loops share (window_test.hip: ScanNet; kitti_window_test.hip: SemanticKITTI): the chunking of
-// a scene into waves of 64 consecutive points and the per-window scan of the chunk histogram.
+// a scene into waves of 64 consecutive points and the per-window scan of the chunk histogram; and what the two SemanticKITTI
+// loops share (kitti_window_test.hip, kitti_block_test.hip): a point's windows as one range per axis and the wave's rectangle.
 #pragma once
 #include "common.hpp"
 
@@ -31,6 +32,26 @@ static __global__ __launch_bounds__(256) void window_scan_kernel(long nchunks, i
     __syncthreads();
   }
   if (threadIdx.x == 0) counts[blockIdx.x] = carry;
+}
+
+struct KWinMember {
+  int xlo, xhi, ylo, yhi;  // an empty range on either axis, or z outside: xhi < xlo
+};
+
+// the rectangle of windows that holds every membership of the wave's 64 points (empty: xhi < xlo): uniform over the wave
+__device__ __forceinline__ KWinMember wave_rect(KWinMember m) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const int a = __shfl_xor(m.xlo, o, 64), b = __shfl_xor(m.xhi, o, 64), c = __shfl_xor(m.ylo, o, 64), d = __shfl_xor(m.yhi, o, 64);
+    m.xlo = a < m.xlo ? a : m.xlo;
+    m.xhi = b > m.xhi ? b : m.xhi;
+    m.ylo = c < m.ylo ? c : m.ylo;
+    m.yhi = d > m.yhi ? d : m.yhi;
+  }
+  m.xlo = __builtin_amdgcn_readfirstlane(m.xlo);  // every lane holds the same four values: the loops over them are scalar
+  m.xhi = __builtin_amdgcn_readfirstlane(m.xhi);
+  m.ylo = __builtin_amdgcn_readfirstlane(m.ylo);
+  m.yhi = __builtin_amdgcn_readfirstlane(m.yhi);
+  return m;
 }
 
 }  // namespace pasnl
