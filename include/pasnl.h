@@ -710,9 +710,10 @@ int pasnl_window_bounds(long n, const float* xyz, float* out_bounds, pasnl_strea
  * a point is a member when its float32 coordinates are >= curmin - 0.2 and <= curmax + 0.2 on all three axes, compared in
  * float64 exactly so (every window of an axis is tested: no index comes out of a division).  bounds: the six device floats
  * of pasnl_window_bounds.  hist: pasnl_window_hist_bytes(n, nx, ny) device bytes -- per window and chunk of 64 consecutive
- * points the member count (a wave ballot), then scanned in place per window to the count in earlier chunks; it is the input
- * of pasnl_window_fill.  -> out_counts (nx*ny) i32, empty windows included.  nx, ny <= 64, else PASNL_EUNSUPPORTED.  Two
- * launches. */
+ * points the member count (cleared, then a wave ballot: a wave stores only for the windows round its own points), then
+ * scanned in place per window to the count in earlier chunks; it is the input of pasnl_window_fill.  -> out_counts (nx*ny)
+ * i32, empty windows included.  No limit per axis: nx * ny <= INT_MAX, else PASNL_EUNSUPPORTED (pasnl_window_hist_bytes: 0).
+ * A clear and two launches. */
 size_t pasnl_window_hist_bytes(long n, int nx, int ny);
 int pasnl_window_count(long n, const float* xyz, const float* bounds, int nx, int ny, double delta, int* hist, int* out_counts,
                        pasnl_stream_t stream);
@@ -869,8 +870,8 @@ int pasnl_block_crop_stats(long n, const float* xyz, const int* labels, const fl
  * curmin = float64(coordmin) + [i * 1.5, j * 1.5, 0] and curmax = float64(coordmin) + [(i + 1) * 1.5, (j + 1) * 1.5,
  * float32(coordmax_z - coordmin_z)] -- the upper bound is NOT curmin + 1.5 as in pasnl_window_count, and rounds
  * differently; membership is the 0.2-margin test of pasnl_block_crop_stats.  hist: pasnl_window_hist_bytes(n, nx, ny) device
- * bytes, as in pasnl_window_count.  -> out_counts (nx*ny) i32, empty columns included.  nx, ny <= 64, else
- * PASNL_EUNSUPPORTED.  Two launches. */
+ * bytes, as in pasnl_window_count.  -> out_counts (nx*ny) i32, empty columns included.  No limit per axis: nx * ny <=
+ * INT_MAX, else PASNL_EUNSUPPORTED.  A clear and two launches. */
 int pasnl_block_grid_count(long n, const float* xyz, const float* bounds, int nx, int ny, int* hist, int* out_counts,
                            pasnl_stream_t stream);
 

@@ -36,10 +36,10 @@ import numpy as np
 import torch
 
 from pointasnl_amd import _hip
+from pointasnl_amd.block_loop import BlockLoop
 from pointasnl_amd.SemanticKITTI.scan_tester import _p
 
-MAX_AXIS = 64  # columns per axis (pasnl_block_grid_count)
-TRIES = 10     # D:40
+TRIES = 10  # D:40
 
 
 def key_span(zext):
@@ -56,7 +56,7 @@ def key_span(zext):
     return key_lo, key_hi - key_lo + 1
 
 
-class BlockTester:
+class BlockTester(BlockLoop):
     """`BlockTester(scenes, labels, colors=None, num_classes=21, block_points=8192, batch_size=8, labelweights=None,
     rng=np.random)`.
 
@@ -120,14 +120,10 @@ class BlockTester:
         self.workspace = torch.zeros((int(_hip.lib().pasnl_block_score_workspace_bytes()),), dtype=torch.uint8, device=dev)
         self.reset()
 
-    def reset(self):
-        """clears the counters and the loss (both loops start with it)"""
-        self.counters.zero_()
-        self.loss.zero_()
-        self.forwards, self.num_batches, self.whole, self.left, self._final = 0, 0, False, 0, None
-
     def _hist(self, i, nx, ny):
         nbytes = int(_hip.lib().pasnl_window_hist_bytes(ctypes.c_long(self.sizes[i]), nx, ny))
+        if nbytes == 0:
+            raise _hip.PasnlUnsupported(f"{nx} x {ny} columns: their positions do not fit an int32")
         return torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device)
 
     # ---- chopped scenes (D:31-64)
@@ -161,8 +157,8 @@ class BlockTester:
                 break
         return centre, m, hist, t + 1
 
-    def _rows(self, i, centre, nx, ny, hist, woff, cap, rowpos, data, seg, smpw, row0=0):
-        """member lists, then rows: rowpos (rows*P,) positions -> rows row0.. of data / seg / smpw"""
+    def _rows(self, i, centre, nx, ny, hist, woff, cap, rowpos, rowbase, data, seg, smpw, row0=0):
+        """member lists, then rows: rowpos (rows*P,) positions -> rows row0.. of data / seg / smpw (rowbase: not needed here)"""
         cat_idx = torch.empty((cap,), dtype=torch.int32, device=self.device)
         cat_mask = torch.empty((cap,), dtype=torch.uint8, device=self.device)
         n = ctypes.c_long(self.sizes[i])
@@ -175,20 +171,6 @@ class BlockTester:
                     _p(self.labels[i]), self.C, _p(self.labelweights), _p(data, row0 * self.P * self.width * 4),
                     _p(seg, row0 * self.P * 4), _p(smpw, row0 * self.P * 4))
 
-    def _item_into(self, i, data, seg, smpw, row):
-        centre, m, hist, _ = self.draw_crop(i)
-        choice = self.rng.choice(m, self.P, replace=True)
-        self._rows(i, centre, 1, 1, hist, self.zero, m, choice, data, seg, smpw, row)
-
-    def item(self, i):
-        """One `ScannetDataset.__getitem__(i)` (D:31-64) on the device: advances the RNG.  -> device tensors data (P,3|6)
-        f32, seg (P,) i32, smpw (P,) f32 = float32(labelweights[seg] * mask)."""
-        data = torch.empty((1, self.P, self.width), dtype=torch.float32, device=self.device)
-        seg = torch.empty((1, self.P), dtype=torch.int32, device=self.device)
-        smpw = torch.empty((1, self.P), dtype=torch.float32, device=self.device)
-        self._item_into(i, data, seg, smpw, 0)
-        return data[0], seg[0], smpw[0]
-
     # ---- whole scenes (D:92-129)
     def grid(self, i):
         """D:100-101 through numpy on the read-back float32 bounds, the reference's own expression -> nx, ny"""
@@ -197,8 +179,6 @@ class BlockTester:
         ny = int(np.ceil((coordmax[1] - coordmin[1]) / 1.5).astype(np.int32))
         if nx < 1 or ny < 1:
             raise ValueError(f"scene {i} has zero extent in x or y: the reference finds no column")
-        if nx > MAX_AXIS or ny > MAX_AXIS:
-            raise _hip.PasnlUnsupported(f"{nx} x {ny} columns: at most {MAX_AXIS} per axis")
         return nx, ny
 
     def column_counts(self, i):
@@ -211,22 +191,9 @@ class BlockTester:
         return (nx, ny), counts.cpu().numpy().astype(np.int64), hist
 
     def scene_blocks(self, i):
-        """One `ScannetDatasetWholeScene.__getitem__(i)` (D:92-129) on the device: one `rng.choice(count, P)` per non-empty
-        column in the reference's order, one fill, one gather.  -> device tensors data (R,P,3|6) f32, seg (R,P) i32, smpw
-        (R,P) f32."""
-        (nx, ny), counts, hist = self.column_counts(i)
-        found = np.flatnonzero(counts > 0)  # D:113-114: empty columns are skipped and draw nothing
-        cap = int(counts.sum())
-        if cap >= 2 ** 31:
-            raise _hip.PasnlUnsupported("the columns hold 2^31 or more members")
-        woff = np.where(counts > 0, np.cumsum(counts) - counts, -1)
-        rowpos = np.concatenate([self.rng.choice(int(counts[w]), self.P, replace=True) + woff[w] for w in found])
-        rows = len(found)
-        data = torch.empty((rows, self.P, self.width), dtype=torch.float32, device=self.device)
-        seg = torch.empty((rows, self.P), dtype=torch.int32, device=self.device)
-        smpw = torch.empty((rows, self.P), dtype=torch.float32, device=self.device)
-        self._rows(i, -1, nx, ny, hist, _hip.as_dev(woff.astype(np.int32), torch.int32), cap, rowpos, data, seg, smpw)
-        return data, seg, smpw
+        """One `ScannetDatasetWholeScene.__getitem__(i)` (D:92-129) on the device -> device tensors data (R,P,3|6) f32, seg
+        (R,P) i32, smpw (R,P) f32"""
+        return self._whole_item(i)
 
     # ---- the loops
     def normalize(self, src, rows, angles=None):
@@ -237,24 +204,6 @@ class BlockTester:
             rot = _hip.as_dev(np.stack([np.cos(angles), np.sin(angles)], axis=1).astype(np.float64), torch.float64)
         _hip.launch("pasnl_block_normalize", "BlockTester normalize", rows, self.P, self.width, _p(src), _hip.ptr(rot), _p(self.batch))
         return self.batch
-
-    def score(self, logits, seg, smpw):
-        """T:311-321 / T:391-402 for one batch of B rows: logits (B,P,C) f32 from the forward"""
-        v = _hip.as_dev(logits, torch.float32)
-        if v.numel() != self.B * self.P * self.C or v.shape[-1] != self.C:
-            raise ValueError(f"the forward must return ({self.B}, {self.P}, {self.C}) logits")
-        _hip.launch("pasnl_block_score", "BlockTester score", self.B, self.P, self.C, _p(v), _p(seg), _p(smpw), _p(self.counters),
-                    _p(self.loss), _p(self.workspace))
-        self.forwards += 1
-
-    def _finish(self, num_batches, whole, left=0):
-        self.num_batches, self.whole, self.left = num_batches, whole, left
-        c = self.counters.cpu().numpy()  # the epoch's one readback of the counters
-        C = self.C
-        self._final = dict(total_correct=int(c[0]), total_seen=int(c[1]), seen=c[2:2 + C].copy(), correct=c[2 + C:2 + 2 * C].copy(),
-                           deno=c[2 + 2 * C:2 + 3 * C].copy(), hist=c[2 + 3 * C:2 + 4 * C].copy(),
-                           loss_sum=float(self.loss.cpu().numpy()[0]))
-        return self.miou()
 
     def run_chopped(self, forward):
         """T:279-329, one epoch over randomly chopped scenes: scenes in index order, S // B batches (the remainder is
@@ -269,65 +218,5 @@ class BlockTester:
             self.score(forward(self.normalize(self.raw, self.B, angles)), self.batch_label, self.batch_smpw)
         return self._finish(num_batches, False)
 
-    def run_whole(self, forward):
-        """T:333-420, one epoch over whole scenes with the reference's carry-over: a scene's rows go in front of the carried
-        ones when no batch is being continued and behind the accumulated ones when one is; fewer than B rows wait for the next
-        scene; of more than B the first B are fed and the rest carried, even when B or more remain -- at most one forward per
-        scene -- and what is left at the end is never scored.  -> mIoU."""
-        self.reset()
-        continuing, rows, carried = False, None, None
-        for i in range(self.S):
-            new = self.scene_blocks(i)
-            if continuing:
-                rows = tuple(torch.cat((r, a), dim=0) for r, a in zip(rows, new))
-            else:
-                rows = new if carried is None else tuple(torch.cat((a, c), dim=0) for a, c in zip(new, carried))
-            continuing = rows[0].shape[0] < self.B
-            if continuing:
-                continue
-            carried = tuple(r[self.B:] for r in rows) if rows[0].shape[0] > self.B else None
-            data, seg, smpw = rows
-            self.score(forward(self.normalize(data, self.B)), seg, smpw)  # (the first B rows of each)
-        left = rows[0].shape[0] if continuing else (0 if carried is None else carried[0].shape[0])
-        return self._finish(self.S, True, left)
-
-    # ---- results
-    def totals(self):
-        """-> dict(total_correct, total_seen, seen (C,), correct (C,), deno (C,), hist (C,)): the int64 counters of the last
-        epoch (T:312-321; hist is T:316-317's label histogram)"""
-        return {k: self._final[k] for k in ("total_correct", "total_seen", "seen", "correct", "deno", "hist")}
-
-    def class_iou(self):
-        """T:322: the IoU of classes 1..C-1, correct / (iou_deno + 1e-6)"""
-        f = self._final
-        return np.array(f["correct"][1:]) / (np.array(f["deno"][1:], dtype=float) + 1e-6)
-
-    def miou(self):
-        return np.mean(self.class_iou())
-
-    def mean_loss(self, extra=0.0):
-        """T:323 / T:405: loss_sum / float(num_batches), where num_batches is S // B for the chopped loop and S -- not the
-        number of forwards -- for the whole-scene loop; extra is what the model's other loss terms add to every forward"""
-        return (self._final["loss_sum"] + float(extra) * self.forwards) / float(self.num_batches)
-
-    def report(self, names, extra=0.0):
-        """The lines T:323-326 or T:405-417 log for the last epoch; names[l] is the class name (seg_label_to_cat).  Where the
-        reference divides by a zero count -- the accuracy without a labelled point, the whole-scene table's IoU of a class
-        with iou_deno == 0 -- numpy's scalar division gives nan with a warning there (the counters are numpy integers, so it
-        is not a ZeroDivisionError); nan is what is reported here."""
-        f = self._final
-        head = "Eval whole scene" if self.whole else "Eval"
-        with np.errstate(divide="ignore", invalid="ignore"):
-            acc = np.float64(f["total_correct"]) / float(f["total_seen"])
-            class_acc = np.mean(np.array(f["correct"][1:]) / (np.array(f["seen"][1:], dtype=float) + 1e-6))
-            lines = ["%s mean loss: %f" % (head, self.mean_loss(extra)), "Eval point avg class IoU: %f" % self.miou(),
-                     "%s point accuracy: %f" % (head, acc), "%s point avg class acc: %f" % (head, class_acc)]
-            if self.whole:
-                hist = f["hist"].astype(np.float64)
-                weights = hist[1:].astype(np.float32) / np.sum(hist[1:].astype(np.float32))
-                txt = "------- IoU --------\n"
-                for l in range(1, self.C):
-                    txt += "class %s weight: %.3f, IoU: %.3f \n" % (names[l] + " " * (14 - len(names[l])), weights[l - 1],
-                                                                    np.int64(f["correct"][l]) / float(f["deno"][l]))
-                lines.append(txt)
-        return lines
+    def _whole_batch(self, data):
+        return self.normalize(data, self.B)  # T:333-420 feeds the whole scenes' rows normalized and unrotated

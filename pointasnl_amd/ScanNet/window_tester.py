@@ -34,7 +34,6 @@ from pointasnl_amd import _hip
 from pointasnl_amd.SemanticKITTI.scan_tester import _p
 
 TEST_CLASS = np.array([0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])  # T:105
-MAX_AXIS = 64  # windows per axis (pasnl_window_count)
 
 
 def nearest_block(center, centers):
@@ -147,8 +146,6 @@ class WindowTester:
         ny = int(np.ceil((coordmax[1] - coordmin[1]) / self.stride).astype(np.int32))
         if nx < 1 or ny < 1:
             raise ValueError(f"scene {i} has zero extent in x or y: the reference finds no window")
-        if nx > MAX_AXIS or ny > MAX_AXIS:
-            raise _hip.PasnlUnsupported(f"{nx} x {ny} windows: at most {MAX_AXIS} per axis")
         return coordmin, coordmax, nx, ny
 
     def count(self, i, nx, ny):
@@ -156,6 +153,8 @@ class WindowTester:
         (nx*ny,) as numpy, the second readback."""
         n = self.sizes[i]
         nbytes = int(_hip.lib().pasnl_window_hist_bytes(ctypes.c_long(n), nx, ny))
+        if nbytes == 0:
+            raise _hip.PasnlUnsupported(f"{nx} x {ny} windows: their positions do not fit an int32")
         hist = torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device)
         counts = torch.empty((nx * ny,), dtype=torch.int32, device=self.device)
         _hip.launch("pasnl_window_count", "WindowTester count", ctypes.c_long(n), _p(self.xyz[i]), _p(self.bounds), nx, ny,

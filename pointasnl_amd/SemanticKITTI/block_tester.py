@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 from pointasnl_amd import _hip
+from pointasnl_amd.block_loop import BlockLoop
 from pointasnl_amd.SemanticKITTI.scan_tester import _p
 
 TRIES = 10  # D:81
@@ -58,7 +59,7 @@ def label_weights_from_content(content):
     return np.power(np.amax(lut[1:]) / lut, 1 / 3.0)
 
 
-class KittiBlockTester:
+class KittiBlockTester(BlockLoop):
     """`KittiBlockTester(scans, labels, remissions=None, num_classes=20, block_points=8192, batch_size=8, block_size=10,
     padding=0.01, label_weights_lut=None, reference_quirks=True, rng=np.random)`.
 
@@ -67,6 +68,8 @@ class KittiBlockTester:
     wide (the reference's with_remission).  block_size: the column's side as the reference holds it (an int or a float: the
     half side is Python's block_size / 2).  label_weights_lut: (num_classes,) float32, default ones
     (`label_weights_from_content` evaluates the reference's table).  rng: np.random or a RandomState."""
+
+    TABLE_IN_CHOPPED = True  # T:315-325: both loops print the per-class table
 
     def __init__(self, scans, labels, remissions=None, num_classes=20, block_points=8192, batch_size=8, block_size=10, padding=0.01,
                  label_weights_lut=None, reference_quirks=True, rng=np.random):
@@ -125,12 +128,6 @@ class KittiBlockTester:
         self.workspace = torch.zeros((int(_hip.lib().pasnl_block_score_workspace_bytes()),), dtype=torch.uint8, device=dev)
         self.reset()
 
-    def reset(self):
-        """clears the counters and the loss (both loops start with it)"""
-        self.counters.zero_()
-        self.loss.zero_()
-        self.forwards, self.num_batches, self.whole, self.left, self._final = 0, 0, False, 0, None
-
     # ---- chopped scans (D:68-109)
     def crop_stats(self, i, centre):
         """One try (D:82-97) round point `centre` of scan i -> (m, labelled, hist): len(cur_semantic_seg) and
@@ -170,20 +167,6 @@ class KittiBlockTester:
                     1 if self.with_remission else 0, _p(self.labels[i]), self.C, _p(self.lut), 1 if self.quirks else 0,
                     _p(data, row0 * self.P * self.width * 4), _p(seg, row0 * self.P * 4), _p(smpw, row0 * self.P * 4))
 
-    def _item_into(self, i, data, seg, smpw, row):
-        centre, m, hist, _ = self.draw_crop(i)
-        choice = self.rng.choice(m, self.P, replace=True)
-        self._rows(i, centre, 1, 1, hist, self.zero, m, choice, [0], data, seg, smpw, row)
-
-    def item(self, i):
-        """One `SemanticKittiDataset.__getitem__(i)` (D:68-109) on the device: advances the RNG.  -> device tensors data
-        (P,3|4) f32, seg (P,) i32, smpw (P,) f32."""
-        data = torch.empty((1, self.P, self.width), dtype=torch.float32, device=self.device)
-        seg = torch.empty((1, self.P), dtype=torch.int32, device=self.device)
-        smpw = torch.empty((1, self.P), dtype=torch.float32, device=self.device)
-        self._item_into(i, data, seg, smpw, 0)
-        return data[0], seg[0], smpw[0]
-
     # ---- whole scans (D:164-211)
     def grid(self, i):
         """D:177-178 through numpy on the read-back float32 bounds, the reference's own expression -> nx, ny"""
@@ -207,22 +190,9 @@ class KittiBlockTester:
         return (nx, ny), counts.cpu().numpy().astype(np.int64), hist
 
     def scan_blocks(self, i):
-        """One `SemanticKittiDataset_whole.__getitem__(i)` (D:164-211) on the device: one `rng.choice(count, P)` per non-empty
-        column in the reference's order, one fill, one gather.  -> device tensors data (R,P,3|4) f32, seg (R,P) i32, smpw
-        (R,P) f32."""
-        (nx, ny), counts, hist = self.column_counts(i)
-        found = np.flatnonzero(counts > 0)  # D:191-192: empty columns are skipped and draw nothing
-        cap = int(counts.sum())
-        if cap >= 2 ** 31:
-            raise _hip.PasnlUnsupported("the columns hold 2^31 or more members")
-        woff = np.where(counts > 0, np.cumsum(counts) - counts, -1)
-        rowpos = np.concatenate([self.rng.choice(int(counts[w]), self.P, replace=True) + woff[w] for w in found])
-        rows = len(found)
-        data = torch.empty((rows, self.P, self.width), dtype=torch.float32, device=self.device)
-        seg = torch.empty((rows, self.P), dtype=torch.int32, device=self.device)
-        smpw = torch.empty((rows, self.P), dtype=torch.float32, device=self.device)
-        self._rows(i, -1, nx, ny, hist, _hip.as_dev(woff.astype(np.int32), torch.int32), cap, rowpos, woff[found], data, seg, smpw)
-        return data, seg, smpw
+        """One `SemanticKittiDataset_whole.__getitem__(i)` (D:164-211) on the device -> device tensors data (R,P,3|4) f32, seg
+        (R,P) i32, smpw (R,P) f32"""
+        return self._whole_item(i)
 
     # ---- the loops
     def rotate(self, src, rows, angles, out=None):
@@ -232,24 +202,6 @@ class KittiBlockTester:
         out = src if out is None else out
         _hip.launch("pasnl_kblock_rotate", "KittiBlockTester rotate", rows, self.P, self.width, _p(src), _p(rot), _p(out))
         return out
-
-    def score(self, logits, seg, smpw):
-        """T:299-310 / T:389-400 for one batch of B rows: logits (B,P,C) f32 from the forward"""
-        v = _hip.as_dev(logits, torch.float32)
-        if v.numel() != self.B * self.P * self.C or v.shape[-1] != self.C:
-            raise ValueError(f"the forward must return ({self.B}, {self.P}, {self.C}) logits")
-        _hip.launch("pasnl_block_score", "KittiBlockTester score", self.B, self.P, self.C, _p(v), _p(seg), _p(smpw), _p(self.counters),
-                    _p(self.loss), _p(self.workspace))
-        self.forwards += 1
-
-    def _finish(self, num_batches, whole, left=0):
-        self.num_batches, self.whole, self.left = num_batches, whole, left
-        c = self.counters.cpu().numpy()  # the epoch's one readback of the counters
-        C = self.C
-        self._final = dict(total_correct=int(c[0]), total_seen=int(c[1]), seen=c[2:2 + C].copy(), correct=c[2 + C:2 + 2 * C].copy(),
-                           deno=c[2 + 2 * C:2 + 3 * C].copy(), hist=c[2 + 3 * C:2 + 4 * C].copy(),
-                           loss_sum=float(self.loss.cpu().numpy()[0]))
-        return self.miou()
 
     def run_chopped(self, forward):
         """T:267-328, one epoch over randomly chopped scans: scans in index order, S // B batches (the remainder is dropped,
@@ -264,64 +216,5 @@ class KittiBlockTester:
             self.score(forward(self.rotate(self.batch, self.B, angles)), self.batch_label, self.batch_smpw)
         return self._finish(num_batches, False)
 
-    def run_whole(self, forward):
-        """T:331-418, one epoch over whole scans with the reference's carry-over: a scan's rows go in front of the carried ones
-        when no batch is being continued and behind the accumulated ones when one is; fewer than B rows wait for the next
-        scan; of more than B the first B are fed, unrotated, and the rest carried, even when B or more remain -- at most one
-        forward per scan -- and what is left at the end is never scored.  -> mIoU."""
-        self.reset()
-        continuing, rows, carried = False, None, None
-        for i in range(self.S):
-            new = self.scan_blocks(i)
-            if continuing:
-                rows = tuple(torch.cat((r, a), dim=0) for r, a in zip(rows, new))
-            else:
-                rows = new if carried is None else tuple(torch.cat((a, c), dim=0) for a, c in zip(new, carried))
-            continuing = rows[0].shape[0] < self.B
-            if continuing:
-                continue
-            carried = tuple(r[self.B:] for r in rows) if rows[0].shape[0] > self.B else None
-            data, seg, smpw = (r[:self.B].contiguous() for r in rows)
-            self.score(forward(data), seg, smpw)
-        left = rows[0].shape[0] if continuing else (0 if carried is None else carried[0].shape[0])
-        return self._finish(self.S, True, left)
-
-    # ---- results
-    def totals(self):
-        """-> dict(total_correct, total_seen, seen (C,), correct (C,), deno (C,), hist (C,)): the int64 counters of the last
-        epoch (T:300-310; hist is T:305-306's label histogram)"""
-        return {k: self._final[k] for k in ("total_correct", "total_seen", "seen", "correct", "deno", "hist")}
-
-    def class_iou(self):
-        """T:313-314: the IoU of classes 1..C-1, correct / (iou_deno + 1e-6)"""
-        f = self._final
-        return np.array(f["correct"][1:]) / (np.array(f["deno"][1:], dtype=float) + 1e-6)
-
-    def miou(self):
-        return np.mean(self.class_iou())
-
-    def mean_loss(self, extra=0.0):
-        """T:315 / T:403: loss_sum / float(num_batches), where num_batches is S // B for the chopped loop and S -- not the
-        number of forwards -- for the whole-scan loop; extra is what the model's other loss terms add to every forward"""
-        return (self._final["loss_sum"] + float(extra) * self.forwards) / float(self.num_batches)
-
-    def report(self, names, extra=0.0):
-        """The lines T:315-325 or T:403-415 log for the last epoch, the per-class table included (both loops print it);
-        names[l] is the class name (seg_label_to_cat).  Where the reference divides by a zero count -- the accuracy without a
-        labelled point, the table's IoU of a class with iou_deno == 0 -- numpy's scalar division gives nan with a warning
-        there; nan is what is reported here."""
-        f = self._final
-        head = "Eval whole scene" if self.whole else "Eval"
-        with np.errstate(divide="ignore", invalid="ignore"):
-            acc = np.float64(f["total_correct"]) / float(f["total_seen"])
-            class_acc = np.mean(np.array(f["correct"][1:]) / (np.array(f["seen"][1:], dtype=float) + 1e-6))
-            lines = ["%s mean loss: %f" % (head, self.mean_loss(extra)), "Eval point avg class IoU: %f" % self.miou(),
-                     "%s point accuracy: %f" % (head, acc), "%s point avg class acc: %f" % (head, class_acc)]
-            hist = f["hist"].astype(np.float64)
-            weights = hist[1:].astype(np.float32) / np.sum(hist[1:].astype(np.float32))
-            txt = "------- IoU --------\n"
-            for l in range(1, self.C):
-                txt += "class %s weight: %.3f, IoU: %.3f \n" % (names[l] + " " * (14 - len(names[l])), weights[l - 1],
-                                                                np.int64(f["correct"][l]) / float(f["deno"][l]))
-            lines.append(txt)
-        return lines
+    def _whole_batch(self, data):
+        return data  # T:331-418 feeds the whole scans' rows as they are

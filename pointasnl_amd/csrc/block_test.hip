@@ -20,50 +20,31 @@
 
 namespace pasnl {
 
-constexpr int BT_WAVES = 4;            // chunks (of 64 consecutive points, one wave each) in flight per workgroup
 constexpr int BT_KEYS = 1 << 19;       // voxel keys the bitmap distinguishes: 64 KiB of LDS per workgroup
 constexpr int BT_MAX_GROUPS = 1024;    // workgroups of the statistics pass (each clears and merges one LDS bitmap)
-constexpr int BT_AXIS_MAX = 64;        // columns per axis: a point's memberships along an axis are one 64-bit mask
 constexpr int BT_CLASS_MAX = 256;      // classes whose counters a workgroup keeps in LDS
 constexpr int BT_SCORE_GROUPS = 256;   // workgroups of the score pass == partial loss sums the last pass adds in order
 
-// ---- the chopped column (D:41-46, 52): float64 bounds from the float32 centre and the float32 z extent of the scene
-struct CropBox {
-  double lo[3], hi[3];
-};
-
-__device__ __forceinline__ CropBox crop_box(const float* __restrict__ centre, const float* __restrict__ b) {
-  CropBox box;
-  box.lo[0] = (double)centre[0] - 0.75;  // curcenter - [0.75, 0.75, 1.5]: float32 array - list -> float64
-  box.hi[0] = (double)centre[0] + 0.75;
-  box.lo[1] = (double)centre[1] - 0.75;
-  box.hi[1] = (double)centre[1] + 0.75;
-  box.lo[2] = (double)b[2];  // curmin[2] = coordmin[2]; curmax[2] = coordmax[2]
-  box.hi[2] = (double)b[5];
-  return box;
-}
-
-__device__ __forceinline__ bool crop_inside(const CropBox& box, const double* p, double margin) {
-  bool in = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) in = in && p[a] >= box.lo[a] - margin && p[a] <= box.hi[a] + margin;
-  return in;
-}
+// ---- the chopped column (D:41-46, 52) is window_scan.hpp's CropBox round the centre with half = 0.75, its mask margin 0.01;
+// the whole-scene grid (D:107-109, 115) is its ColumnGrid with curmin = float64(coordmin) + i * 1.5,
+// curmax = float64(coordmin) + (i + 1) * 1.5 (i * 1.5 and (i + 1) * 1.5 are exact), its mask margin 0.001
+constexpr double BT_HALF = 0.75;
+static inline ColumnGrid block_grid(long centre, int nx, int ny) { return {nx, ny, 1.5, 1.5, true, 0.2, centre >= 0 ? 0.01 : 0.001}; }
 
 // Pass 1 of a try, one wave per chunk: hist[c] = members (0.2 margin), hist[nchunks + c] = members with label > 0 (two
 // ballots, no atomics), and the voxel key of every member inside the 0.01 margin set in the workgroup's LDS bitmap, which is
 // OR-merged into bitmap[1 + word] at the end; bitmap[0] flags a key outside [key_lo, key_lo + 32 * words) or a NaN key.
-__global__ __launch_bounds__(64 * BT_WAVES) void block_crop_stats_kernel(long n, const float* __restrict__ xyz, const int* __restrict__ labels,
+__global__ __launch_bounds__(64 * COL_WAVES) void block_crop_stats_kernel(long n, const float* __restrict__ xyz, const int* __restrict__ labels,
                                                                          const float* __restrict__ bounds, long centre, double key_lo,
                                                                          int words, long nchunks, int* __restrict__ hist,
                                                                          unsigned* __restrict__ bitmap) {
   extern __shared__ unsigned bits[];
   const int tid = threadIdx.x, lane = tid & 63;
-  for (int k = tid; k < words; k += 64 * BT_WAVES) bits[k] = 0u;
+  for (int k = tid; k < words; k += 64 * COL_WAVES) bits[k] = 0u;
   __syncthreads();
-  const CropBox box = crop_box(xyz + centre * 3, bounds);
+  const CropBox box = crop_box(xyz + centre * 3, bounds, BT_HALF);
   const double span = (double)words * 32.0;
-  for (long c = (long)blockIdx.x * BT_WAVES + (tid >> 6); c < nchunks; c += (long)gridDim.x * BT_WAVES) {  // (wave-uniform)
+  for (long c = (long)blockIdx.x * COL_WAVES + (tid >> 6); c < nchunks; c += (long)gridDim.x * COL_WAVES) {  // (wave-uniform)
     const long p = c * 64 + lane;
     bool in20 = false, in1 = false, lab = false;
     double q[3] = {0.0, 0.0, 0.0};
@@ -93,7 +74,7 @@ __global__ __launch_bounds__(64 * BT_WAVES) void block_crop_stats_kernel(long n,
     }
   }
   __syncthreads();
-  for (int k = tid; k < words; k += 64 * BT_WAVES) {
+  for (int k = tid; k < words; k += 64 * COL_WAVES) {
     const unsigned v = bits[k];
     if (v) atomicOr(&bitmap[1 + k], v);
   }
@@ -110,99 +91,6 @@ __global__ __launch_bounds__(256) void block_unique_kernel(int words, const unsi
   if (threadIdx.x == 0) {
     stats[2] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
     stats[3] = (int)bitmap[0];
-  }
-}
-
-// ---- membership of a point in the columns, as masks (the form of window_test.hip's WinMember)
-struct BlockMember {
-  unsigned long long x20, y20, x1, y1;
-  bool z20, z1;
-};
-
-// the whole-scene grid (D:107-109, 115): curmin = float64(coordmin) + i * 1.5, curmax = float64(coordmin) + (i + 1) * 1.5 --
-// NOT curmin + 1.5, which rounds differently; i * 1.5 and (i + 1) * 1.5 are exact
-__device__ __forceinline__ void grid_axis_masks(double p, double origin, int count, unsigned long long& m20, unsigned long long& m1) {
-  m20 = 0ull;
-  m1 = 0ull;
-  for (int i = 0; i < count; ++i) {
-    const double curmin = origin + (double)i * 1.5;
-    const double curmax = origin + (double)(i + 1) * 1.5;
-    if (p >= curmin - 0.2 && p <= curmax + 0.2) m20 |= 1ull << i;
-    if (p >= curmin - 0.001 && p <= curmax + 0.001) m1 |= 1ull << i;
-  }
-}
-
-__device__ __forceinline__ BlockMember grid_member(const float* __restrict__ p, const float* __restrict__ b, int nx, int ny) {
-  BlockMember m;
-  grid_axis_masks((double)p[0], (double)b[0], nx, m.x20, m.x1);
-  grid_axis_masks((double)p[1], (double)b[1], ny, m.y20, m.y1);
-  const double pz = (double)p[2];
-  const double zmin = (double)b[2] + 0.0;
-  const double zmax = (double)b[2] + (double)(b[5] - b[2]);  // coordmin + [.., .., coordmax[2] - coordmin[2]]: a float32 difference
-  m.z20 = pz >= zmin - 0.2 && pz <= zmax + 0.2;
-  m.z1 = pz >= zmin - 0.001 && pz <= zmax + 0.001;
-  return m;
-}
-
-// the chopped column as the single "window" 0 of the same form (the 0.01 margin in the *1 fields)
-__device__ __forceinline__ BlockMember crop_member(const float* __restrict__ p, const CropBox& box) {
-  const double q[3] = {(double)p[0], (double)p[1], (double)p[2]};
-  BlockMember m = {0ull, 0ull, 0ull, 0ull, false, false};
-  m.x20 = q[0] >= box.lo[0] - 0.2 && q[0] <= box.hi[0] + 0.2;
-  m.y20 = q[1] >= box.lo[1] - 0.2 && q[1] <= box.hi[1] + 0.2;
-  m.z20 = q[2] >= box.lo[2] - 0.2 && q[2] <= box.hi[2] + 0.2;
-  m.x1 = q[0] >= box.lo[0] - 0.01 && q[0] <= box.hi[0] + 0.01;
-  m.y1 = q[1] >= box.lo[1] - 0.01 && q[1] <= box.hi[1] + 0.01;
-  m.z1 = q[2] >= box.lo[2] - 0.01 && q[2] <= box.hi[2] + 0.01;
-  return m;
-}
-
-// whole scene, pass 1: hist[w][chunk] = members of column w among the chunk's 64 points (a ballot: no atomics at all)
-__global__ __launch_bounds__(64 * BT_WAVES) void block_grid_count_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
-                                                                         int nx, int ny, long nchunks, int* __restrict__ hist) {
-  const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * BT_WAVES + (threadIdx.x >> 6);
-  if (c >= nchunks) return;  // whole waves leave
-  const long p = c * 64 + lane;
-  BlockMember m = {0ull, 0ull, 0ull, 0ull, false, false};
-  if (p < n) m = grid_member(xyz + p * 3, bounds, nx, ny);
-  for (int i = 0; i < nx; ++i) {
-    const bool fx = m.z20 && ((m.x20 >> i) & 1ull);
-    for (int j = 0; j < ny; ++j) {
-      const unsigned long long ballot = __ballot(fx && ((m.y20 >> j) & 1ull));
-      if (lane == 0) hist[(size_t)(i * ny + j) * nchunks + c] = __popcll(ballot);
-    }
-  }
-}
-
-// both loops, the last pass: a member's place is woff[w] + (members in earlier chunks) + (members among the lower lanes):
-// ascending scene index.  centre >= 0: the chopped column round that point (nx = ny = 1); centre < 0: the grid.
-__global__ __launch_bounds__(64 * BT_WAVES) void block_fill_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
-                                                                   long centre, int nx, int ny, long nchunks, const int* __restrict__ hist,
-                                                                   const int* __restrict__ woff, long cap, int* __restrict__ out_idx,
-                                                                   unsigned char* __restrict__ out_mask) {
-  const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * BT_WAVES + (threadIdx.x >> 6);
-  if (c >= nchunks) return;
-  const long p = c * 64 + lane;
-  BlockMember m = {0ull, 0ull, 0ull, 0ull, false, false};
-  if (p < n) m = centre >= 0 ? crop_member(xyz + p * 3, crop_box(xyz + centre * 3, bounds)) : grid_member(xyz + p * 3, bounds, nx, ny);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int i = 0; i < nx; ++i) {
-    const bool fx = m.z20 && ((m.x20 >> i) & 1ull);
-    for (int j = 0; j < ny; ++j) {
-      const bool in = fx && ((m.y20 >> j) & 1ull);
-      const unsigned long long ballot = __ballot(in);
-      const int w = i * ny + j;
-      if (in) {
-        const int off = woff[w];
-        const long pos = (long)off + hist[(size_t)w * nchunks + c] + __popcll(ballot & below);
-        if (off >= 0 && pos < cap) {  // (the host sizes the lists from the counts: always taken for a listed column)
-          out_idx[pos] = (int)p;
-          out_mask[pos] = (m.z1 && ((m.x1 >> i) & 1ull) && ((m.y1 >> j) & 1ull)) ? 1 : 0;
-        }
-      }
-    }
   }
 }
 
@@ -368,9 +256,9 @@ extern "C" int pasnl_block_crop_stats(long n, const float* xyz, const int* label
   hipStream_t s = pasnl_hip_stream(stream);
   const long nchunks = wt_chunks(n);
   const int words = (int)((span + 31) / 32);
-  const unsigned groups = wt_blocks(nchunks, BT_WAVES) < (unsigned)BT_MAX_GROUPS ? wt_blocks(nchunks, BT_WAVES) : (unsigned)BT_MAX_GROUPS;
+  const unsigned groups = wt_blocks(nchunks, COL_WAVES) < (unsigned)BT_MAX_GROUPS ? wt_blocks(nchunks, COL_WAVES) : (unsigned)BT_MAX_GROUPS;
   if (hipMemsetAsync(bitmap, 0, (size_t)(1 + words) * sizeof(unsigned), s) != hipSuccess) return PASNL_ELAUNCH;
-  const int rc = launch(block_crop_stats_kernel, dim3(groups), dim3(64 * BT_WAVES), (size_t)words * sizeof(unsigned), s, n, xyz, labels, bounds,
+  const int rc = launch(block_crop_stats_kernel, dim3(groups), dim3(64 * COL_WAVES), (size_t)words * sizeof(unsigned), s, n, xyz, labels, bounds,
                         centre, (double)key_lo, words, nchunks, hist, bitmap);
   if (rc != PASNL_OK) return rc;
   hipLaunchKernelGGL(window_scan_kernel, dim3(2), dim3(256), 0, s, nchunks, hist, out_stats);
@@ -381,26 +269,18 @@ extern "C" int pasnl_block_crop_stats(long n, const float* xyz, const int* label
 extern "C" int pasnl_block_grid_count(long n, const float* xyz, const float* bounds, int nx, int ny, int* hist, int* out_counts,
                                       pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0, PASNL_EINVAL);
-  PASNL_REQUIRE(nx <= BT_AXIS_MAX && ny <= BT_AXIS_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(wt_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
   PASNL_REQUIRE(xyz && bounds && hist && out_counts, PASNL_ENULL);
-  hipStream_t s = pasnl_hip_stream(stream);
-  const long nchunks = wt_chunks(n);
-  hipLaunchKernelGGL(block_grid_count_kernel, dim3(wt_blocks(nchunks, BT_WAVES)), dim3(64 * BT_WAVES), 0, s, n, xyz, bounds, nx, ny, nchunks,
-                     hist);
-  hipLaunchKernelGGL(window_scan_kernel, dim3(nx * ny), dim3(256), 0, s, nchunks, hist, out_counts);
-  return pasnl_launch_status();
+  return wt_count(n, xyz, bounds, block_grid(-1, nx, ny), hist, out_counts, pasnl_hip_stream(stream));
 }
 
 extern "C" int pasnl_block_fill(long n, const float* xyz, const float* bounds, long centre, int nx, int ny, const int* hist, const int* woff,
                                 long cap, int* out_idx, unsigned char* out_mask, pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0 && cap > 0 && centre < n && (centre < 0 || (nx == 1 && ny == 1)),
                 PASNL_EINVAL);
-  PASNL_REQUIRE(nx <= BT_AXIS_MAX && ny <= BT_AXIS_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(wt_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
   PASNL_REQUIRE(xyz && bounds && hist && woff && out_idx && out_mask, PASNL_ENULL);
-  const long nchunks = wt_chunks(n);
-  hipLaunchKernelGGL(block_fill_kernel, dim3(wt_blocks(nchunks, BT_WAVES)), dim3(64 * BT_WAVES), 0, pasnl_hip_stream(stream), n, xyz, bounds,
-                     centre, nx, ny, nchunks, hist, woff, cap, out_idx, out_mask);
-  return pasnl_launch_status();
+  return wt_fill(n, xyz, bounds, block_grid(centre, nx, ny), centre, BT_HALF, hist, woff, cap, out_idx, out_mask, pasnl_hip_stream(stream));
 }
 
 extern "C" int pasnl_block_gather(int rows, int block_points, const int* rowpos, long cap, const int* cat_idx, const unsigned char* cat_mask,

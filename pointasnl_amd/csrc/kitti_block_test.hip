@@ -4,176 +4,50 @@
 // `SemanticKittiDataset_whole.__getitem__` (every non-empty column of a non-overlapping block_size grid, resampled likewise),
 // SemanticKITTI/train_semantic_kitti.py (T) :267-328 `eval_one_epoch` and :331-418 `eval_whole_scene_one_epoch`, and
 // utils/provider.py (P) :71-89 `rotate_point_cloud_z`.  The sibling of block_test.hip for lidar scans: the column's side and
-// the mask's padding are parameters, there is no voxel key and no normalize_data, the grid has no limit per axis (a wave
-// visits only the columns round its own points, as in kitti_window_test.hip), the weight is a float32 table looked up the
-// reference's way, and the remission column is the reference's.  The scan kernel and the chunking are window_scan.hpp's, the
-// bounds pasnl_window_bounds and the score pasnl_block_score.  Everything that has to equal numpy is done in numpy's dtypes
-// (the library builds with -ffp-contract=off); the contract is stated in include/pasnl.h per entry point and restated on the
-// host in tests/kitti_block_flow_ref.py.
+// the mask's padding are parameters, there is no voxel key and no normalize_data, the weight is a float32 table looked up the
+// reference's way, and the remission column is the reference's.  The count, scan and fill kernels and the crop box are
+// window_scan.hpp's, the bounds pasnl_window_bounds and the score pasnl_block_score.  Everything that has to equal numpy is
+// done in numpy's dtypes (the library builds with -ffp-contract=off); the contract is stated in include/pasnl.h per entry
+// point and restated on the host in tests/kitti_block_flow_ref.py.
 //
 // What stays on the host: the numpy RNG stream (the centre of every try, the resampling choices, the rotation angles), the
 // acceptance test of a try (one Python-float comparison on two integers) and the carry-over of rows between scans.
 //   chopped: per try pasnl_kblock_crop_stats -> [two integers down]; then [choices up] -> pasnl_kblock_fill -> pasnl_kblock_gather
 //   whole:   pasnl_kblock_grid_count -> [nx*ny counts down; choices up] -> pasnl_kblock_fill -> pasnl_kblock_gather
 //   per batch, with no synchronisation: (chopped: pasnl_kblock_rotate ->) forward -> pasnl_block_score
-#include <limits.h>
 #include <math.h>
 #include "common.hpp"
 #include "window_scan.hpp"
 
 namespace pasnl {
 
-constexpr int KB_WAVES = 4;        // chunks (of 64 consecutive points, one wave each) per workgroup
 constexpr int KB_CLASS_MAX = 256;  // classes of the weight table (pasnl_block_score's limit: the rows are scored by it)
 constexpr double KB_OUTER = 0.2;   // the margin of membership (D:87, D:187)
 
-// ---- the chopped column (D:82-86): float64 bounds round the float32 centre, z from the float32 extent of the scan
-struct KBox {
-  double lo[3], hi[3];
-};
-
-__device__ __forceinline__ KBox kcrop_box(const float* __restrict__ centre, const float* __restrict__ b, double half) {
-  KBox box;
-  box.lo[0] = (double)centre[0] - half;  // curcenter - [block_size / 2, block_size / 2, 14]: float32 array - list -> float64
-  box.hi[0] = (double)centre[0] + half;
-  box.lo[1] = (double)centre[1] - half;
-  box.hi[1] = (double)centre[1] + half;
-  box.lo[2] = (double)b[2];  // curmin[2] = coordmin[2]; curmax[2] = coordmax[2]
-  box.hi[2] = (double)b[5];
-  return box;
-}
-
-__device__ __forceinline__ bool kbox_inside(const KBox& box, const double* p, double margin) {
-  bool in = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) in = in && p[a] >= box.lo[a] - margin && p[a] <= box.hi[a] + margin;
-  return in;
-}
+// ---- the chopped column (D:82-86) is window_scan.hpp's CropBox round the centre with half = block_size / 2; the whole-scan
+// grid (D:184-187) is its ColumnGrid with curmin = float64(coordmin) + i * block, curmax = float64(coordmin) + (i + 1) * block;
+// the mask (D:95, D:193) is either's test with `padding`
+static inline ColumnGrid kblock_grid(int nx, int ny, double block, double padding) { return {nx, ny, block, block, true, KB_OUTER, padding}; }
 
 // One try, one wave per chunk: hist[c] = members, hist[nchunks + c] = members with label > 0 (two ballots, no atomics)
-__global__ __launch_bounds__(64 * KB_WAVES) void kblock_crop_stats_kernel(long n, const float* __restrict__ xyz, const int* __restrict__ labels,
+__global__ __launch_bounds__(64 * COL_WAVES) void kblock_crop_stats_kernel(long n, const float* __restrict__ xyz, const int* __restrict__ labels,
                                                                           const float* __restrict__ bounds, long centre, double half,
                                                                           long nchunks, int* __restrict__ hist) {
   const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * KB_WAVES + (threadIdx.x >> 6);
+  const long c = (long)blockIdx.x * COL_WAVES + (threadIdx.x >> 6);
   if (c >= nchunks) return;  // whole waves leave
-  const KBox box = kcrop_box(xyz + centre * 3, bounds, half);
+  const CropBox box = crop_box(xyz + centre * 3, bounds, half);
   const long p = c * 64 + lane;
   bool in = false, lab = false;
   if (p < n) {
     const double q[3] = {(double)xyz[p * 3], (double)xyz[p * 3 + 1], (double)xyz[p * 3 + 2]};
-    in = kbox_inside(box, q, KB_OUTER);
+    in = crop_inside(box, q, KB_OUTER);
     lab = in && labels[p] > 0;
   }
   const unsigned long long bin = __ballot(in), blab = __ballot(lab);
   if (lane == 0) {
     hist[c] = __popcll(bin);
     hist[nchunks + c] = __popcll(blab);
-  }
-}
-
-// ---- the whole-scan grid (D:184-187): curmin = float64(coordmin) + i * block, curmax = float64(coordmin) + (i + 1) * block
-// -- NOT curmin + block.  The columns of one axis that hold coordinate p: lo..hi, none when hi < lo; every column of the axis
-// is tested with the reference's own comparison, no index is derived from a division.  Both bounds are monotone in i, so the
-// members are one contiguous range (window_scan.hpp's KWinMember; wave_rect is the wave's rectangle of them).
-__device__ __forceinline__ void kgrid_axis_range(double p, double origin, int count, double block, int& lo, int& hi) {
-  lo = count;
-  hi = -1;
-  for (int i = 0; i < count; ++i) {
-    const double curmin = origin + (double)i * block;
-    const double curmax = origin + (double)(i + 1) * block;
-    if (p >= curmin - KB_OUTER && p <= curmax + KB_OUTER) {
-      lo = i < lo ? i : lo;
-      hi = i;
-    }
-  }
-}
-
-__device__ __forceinline__ double kgrid_zmax(const float* __restrict__ b) {
-  return (double)b[2] + (double)(b[5] - b[2]);  // coordmin + [.., .., coordmax[2] - coordmin[2]]: a float32 difference
-}
-
-__device__ __forceinline__ KWinMember kgrid_member(const float* __restrict__ p, const float* __restrict__ b, int nx, int ny, double block) {
-  KWinMember m;
-  kgrid_axis_range((double)p[0], (double)b[0], nx, block, m.xlo, m.xhi);
-  kgrid_axis_range((double)p[1], (double)b[1], ny, block, m.ylo, m.yhi);
-  const double pz = (double)p[2];
-  const double zmin = (double)b[2] + 0.0;
-  const bool z = pz >= zmin - KB_OUTER && pz <= kgrid_zmax(b) + KB_OUTER;
-  if (!z || m.yhi < m.ylo || m.xhi < m.xlo) m = {nx, -1, ny, -1};
-  return m;
-}
-
-// the mask of D:193 for column (i, j): the same test with `padding`
-__device__ __forceinline__ bool kgrid_mask(const float* __restrict__ p, const float* __restrict__ b, int i, int j, double block, double padding) {
-  const double px = (double)p[0], py = (double)p[1], pz = (double)p[2];
-  const double xmin = (double)b[0] + (double)i * block, xmax = (double)b[0] + (double)(i + 1) * block;
-  const double ymin = (double)b[1] + (double)j * block, ymax = (double)b[1] + (double)(j + 1) * block;
-  const double zmin = (double)b[2] + 0.0, zmax = kgrid_zmax(b);
-  return px >= xmin - padding && px <= xmax + padding && py >= ymin - padding && py <= ymax + padding && pz >= zmin - padding &&
-         pz <= zmax + padding;
-}
-
-// whole scan, pass 1: hist[w][chunk] = members of column w among the chunk's 64 points (a ballot: no atomics at all).  hist
-// is cleared beforehand: a wave stores only for the columns that hold one of its points.
-__global__ __launch_bounds__(64 * KB_WAVES) void kblock_grid_count_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
-                                                                          int nx, int ny, double block, long nchunks, int* __restrict__ hist) {
-  const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * KB_WAVES + (threadIdx.x >> 6);
-  if (c >= nchunks) return;
-  const long p = c * 64 + lane;
-  KWinMember m = {nx, -1, ny, -1};
-  if (p < n) m = kgrid_member(xyz + p * 3, bounds, nx, ny, block);
-  const KWinMember r = wave_rect(m);
-  for (int i = r.xlo; i <= r.xhi; ++i) {
-    const bool fx = i >= m.xlo && i <= m.xhi;
-    for (int j = r.ylo; j <= r.yhi; ++j) {
-      const unsigned long long ballot = __ballot(fx && j >= m.ylo && j <= m.yhi);
-      if (ballot != 0ull && lane == 0) hist[((size_t)i * ny + j) * nchunks + c] = __popcll(ballot);
-    }
-  }
-}
-
-// both loops, the last pass: a member's place is woff[w] + (members in earlier chunks) + (members among the lower lanes):
-// ascending scan index.  centre >= 0: the chopped column round that point (nx = ny = 1); centre < 0: the grid.
-__global__ __launch_bounds__(64 * KB_WAVES) void kblock_fill_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
-                                                                    long centre, double half, int nx, int ny, double block, double padding,
-                                                                    long nchunks, const int* __restrict__ hist, const int* __restrict__ woff,
-                                                                    long cap, int* __restrict__ out_idx, unsigned char* __restrict__ out_mask) {
-  const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * KB_WAVES + (threadIdx.x >> 6);
-  if (c >= nchunks) return;
-  const long p = c * 64 + lane;
-  const bool crop = centre >= 0;
-  KWinMember m = {nx, -1, ny, -1};
-  bool crop_mask = false;
-  if (p < n) {
-    if (crop) {
-      const KBox box = kcrop_box(xyz + centre * 3, bounds, half);
-      const double q[3] = {(double)xyz[p * 3], (double)xyz[p * 3 + 1], (double)xyz[p * 3 + 2]};
-      if (kbox_inside(box, q, KB_OUTER)) m = {0, 0, 0, 0};
-      crop_mask = kbox_inside(box, q, padding);
-    } else {
-      m = kgrid_member(xyz + p * 3, bounds, nx, ny, block);
-    }
-  }
-  const KWinMember r = wave_rect(m);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int i = r.xlo; i <= r.xhi; ++i) {
-    const bool fx = i >= m.xlo && i <= m.xhi;
-    for (int j = r.ylo; j <= r.yhi; ++j) {
-      const bool in = fx && j >= m.ylo && j <= m.yhi;
-      const unsigned long long ballot = __ballot(in);
-      if (in) {
-        const size_t w = (size_t)i * ny + j;
-        const int off = woff[w];
-        const long pos = (long)off + hist[w * nchunks + c] + __popcll(ballot & below);
-        if (off >= 0 && pos < cap) {  // (the host sizes the lists from the counts: always taken for a listed column)
-          out_idx[pos] = (int)p;
-          out_mask[pos] = (crop ? crop_mask : kgrid_mask(xyz + p * 3, bounds, i, j, block, padding)) ? 1 : 0;
-        }
-      }
-    }
   }
 }
 
@@ -232,16 +106,13 @@ __global__ __launch_bounds__(256) void kblock_rotate_kernel(long entries, int bl
 
 using namespace pasnl;
 
-// what the columns' positions must fit: w = i * ny + j and the launch of one workgroup per column
-static inline bool kb_grid_ok(int nx, int ny) { return (long)nx * (long)ny <= (long)INT_MAX; }
-
 extern "C" int pasnl_kblock_crop_stats(long n, const float* xyz, const int* labels, const float* bounds, long centre, double half, int* hist,
                                        int* out_stats, pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && centre >= 0 && centre < n && half >= 0.0 && half < INFINITY, PASNL_EINVAL);
   PASNL_REQUIRE(xyz && labels && bounds && hist && out_stats, PASNL_ENULL);
   hipStream_t s = pasnl_hip_stream(stream);
   const long nchunks = wt_chunks(n);
-  hipLaunchKernelGGL(kblock_crop_stats_kernel, dim3(wt_blocks(nchunks, KB_WAVES)), dim3(64 * KB_WAVES), 0, s, n, xyz, labels, bounds, centre,
+  hipLaunchKernelGGL(kblock_crop_stats_kernel, dim3(wt_blocks(nchunks, COL_WAVES)), dim3(64 * COL_WAVES), 0, s, n, xyz, labels, bounds, centre,
                      half, nchunks, hist);
   hipLaunchKernelGGL(window_scan_kernel, dim3(2), dim3(256), 0, s, nchunks, hist, out_stats);
   return pasnl_launch_status();
@@ -250,15 +121,9 @@ extern "C" int pasnl_kblock_crop_stats(long n, const float* xyz, const int* labe
 extern "C" int pasnl_kblock_grid_count(long n, const float* xyz, const float* bounds, int nx, int ny, double block, int* hist, int* out_counts,
                                        pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0 && block > 0.0 && block < INFINITY, PASNL_EINVAL);
-  PASNL_REQUIRE(kb_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(wt_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
   PASNL_REQUIRE(xyz && bounds && hist && out_counts, PASNL_ENULL);
-  hipStream_t s = pasnl_hip_stream(stream);
-  const long nchunks = wt_chunks(n);
-  if (hipMemsetAsync(hist, 0, (size_t)nx * (size_t)ny * (size_t)nchunks * sizeof(int), s) != hipSuccess) return PASNL_ELAUNCH;
-  hipLaunchKernelGGL(kblock_grid_count_kernel, dim3(wt_blocks(nchunks, KB_WAVES)), dim3(64 * KB_WAVES), 0, s, n, xyz, bounds, nx, ny, block,
-                     nchunks, hist);
-  hipLaunchKernelGGL(window_scan_kernel, dim3((unsigned)(nx * ny)), dim3(256), 0, s, nchunks, hist, out_counts);
-  return pasnl_launch_status();
+  return wt_count(n, xyz, bounds, kblock_grid(nx, ny, block, 0.0), hist, out_counts, pasnl_hip_stream(stream));
 }
 
 extern "C" int pasnl_kblock_fill(long n, const float* xyz, const float* bounds, long centre, double half, int nx, int ny, double block,
@@ -266,12 +131,10 @@ extern "C" int pasnl_kblock_fill(long n, const float* xyz, const float* bounds, 
                                  pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0 && cap > 0 && centre < n && padding == padding, PASNL_EINVAL);
   PASNL_REQUIRE(centre >= 0 ? (nx == 1 && ny == 1 && half >= 0.0 && half < INFINITY) : (block > 0.0 && block < INFINITY), PASNL_EINVAL);
-  PASNL_REQUIRE(kb_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(wt_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
   PASNL_REQUIRE(xyz && bounds && hist && woff && out_idx && out_mask, PASNL_ENULL);
-  const long nchunks = wt_chunks(n);
-  hipLaunchKernelGGL(kblock_fill_kernel, dim3(wt_blocks(nchunks, KB_WAVES)), dim3(64 * KB_WAVES), 0, pasnl_hip_stream(stream), n, xyz, bounds,
-                     centre, half, nx, ny, block, padding, nchunks, hist, woff, cap, out_idx, out_mask);
-  return pasnl_launch_status();
+  return wt_fill(n, xyz, bounds, kblock_grid(nx, ny, block, padding), centre, half, hist, woff, cap, out_idx, out_mask,
+                 pasnl_hip_stream(stream));
 }
 
 extern "C" int pasnl_kblock_gather(int rows, int block_points, const int* rowpos, const int* rowbase, long cap, const int* cat_idx,

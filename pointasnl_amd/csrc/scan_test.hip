@@ -139,12 +139,7 @@ __global__ __launch_bounds__(256) void scratch_init_kernel(long n, int* __restri
   if (i < n) win[i] = -1;
 }
 
-// ---- votes: crop `c` of the batch
-__global__ __launch_bounds__(256) void vote_mark_kernel(int num_point, const int* __restrict__ select, int* __restrict__ win) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j < num_point) atomicMax(&win[select[j]], j);
-}
-
+// ---- votes: crop `c` of the batch (the mark is test_loop.hpp's vote_mark_kernel)
 constexpr int VOTE_MAXC = 64;
 
 __global__ __launch_bounds__(256) void vote_apply_kernel(int num_point, int nc, const float* __restrict__ values, int is_logits,
@@ -157,12 +152,8 @@ __global__ __launch_bounds__(256) void vote_apply_kernel(int num_point, int nc, 
   if (__hip_atomic_load(&win[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != j) return;
   const float* v = values + (size_t)j * nc;
   float p[VOTE_MAXC];
-  if (is_logits) {  // tf.nn.softmax: exp(x - max) / sum, in float32
-    float m = v[0];
-    for (int q = 1; q < nc; ++q) m = v[q] > m ? v[q] : m;
-    float s = 0.0f;
-    for (int q = 0; q < nc; ++q) { p[q] = expf(v[q] - m); s += p[q]; }
-    for (int q = 0; q < nc; ++q) p[q] = p[q] / s;
+  if (is_logits) {
+    vote_softmax(v, nc, p);
   } else {
     for (int q = 0; q < nc; ++q) p[q] = v[q];
   }

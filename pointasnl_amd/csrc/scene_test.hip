@@ -15,6 +15,7 @@
 #include <math.h>
 #include "common.hpp"
 #include "test_loop.hpp"
+#include "window_scan.hpp"
 
 namespace pasnl {
 
@@ -104,12 +105,7 @@ __global__ __launch_bounds__(ST_THREADS) void scene_update_kernel(int num_point,
   if (threadIdx.x == 0) min_potentials[d.cloud] = mn;
 }
 
-// ---- votes: crop `c` of the batch, float32 table of nc = C - 1 classes
-__global__ __launch_bounds__(256) void scene_vote_mark_kernel(int num_point, const int* __restrict__ select, int* __restrict__ win) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j < num_point) atomicMax(&win[select[j]], j);
-}
-
+// ---- votes: crop `c` of the batch, float32 table of nc = C - 1 classes (the mark is test_loop.hpp's vote_mark_kernel)
 constexpr int SV_MAXC = 64;
 
 __global__ __launch_bounds__(256) void scene_vote_apply_kernel(int num_point, int nc, const float* __restrict__ values, int is_logits,
@@ -121,13 +117,8 @@ __global__ __launch_bounds__(256) void scene_vote_apply_kernel(int num_point, in
   const int i = select[j];
   if (__hip_atomic_load(&win[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != j) return;
   float p[SV_MAXC];
-  if (is_logits) {  // tf.nn.softmax(pred[:, :, 1:]): rows of nc + 1 logits, column 0 dropped; exp(x - max) / sum in float32
-    const float* v = values + (size_t)j * (nc + 1) + 1;
-    float m = v[0];
-    for (int q = 1; q < nc; ++q) m = v[q] > m ? v[q] : m;
-    float s = 0.0f;
-    for (int q = 0; q < nc; ++q) { p[q] = expf(v[q] - m); s += p[q]; }
-    for (int q = 0; q < nc; ++q) p[q] = p[q] / s;
+  if (is_logits) {  // tf.nn.softmax(pred[:, :, 1:]): rows of nc + 1 logits, column 0 dropped
+    vote_softmax(values + (size_t)j * (nc + 1) + 1, nc, p);
   } else {
     const float* v = values + (size_t)j * nc;
     for (int q = 0; q < nc; ++q) p[q] = v[q];
@@ -201,7 +192,6 @@ __global__ __launch_bounds__(256) void confusion_kernel(long n, const int* __res
 
 using namespace pasnl;
 
-static inline unsigned sc_blocks(long n, int t) { return (unsigned)((n + t - 1) / t); }
 
 extern "C" int pasnl_scene_order_gather(int b, const pasnl_scene_crop_t* desc, const float* points, const float* colors, int nfeat,
                                         const int* idx, const double* d2, int kcap, const int* perm, int num_point, int abs_coords,
@@ -232,11 +222,11 @@ extern "C" int pasnl_scene_vote(int b, int num_point, int nc, const float* value
   if (b == 0) return PASNL_OK;
   PASNL_REQUIRE(values && select && cloud && offsets && test_probs && win, PASNL_ENULL);
   hipStream_t s = pasnl_hip_stream(stream);
-  const unsigned g = sc_blocks(num_point, 256);
+  const unsigned g = wt_blocks(num_point, 256);
   const size_t width = (size_t)(is_logits ? nc + 1 : nc);
   for (int i = 0; i < b; ++i) {  // crop after crop: a later crop of the batch smooths what the earlier one wrote
     const int* sel = select + (size_t)i * num_point;
-    hipLaunchKernelGGL(scene_vote_mark_kernel, dim3(g), dim3(256), 0, s, num_point, sel, win);
+    hipLaunchKernelGGL(vote_mark_kernel, dim3(g), dim3(256), 0, s, num_point, sel, win);
     hipLaunchKernelGGL(scene_vote_apply_kernel, dim3(g), dim3(256), 0, s, num_point, nc, values + (size_t)i * num_point * width,
                        is_logits, sel, cloud + i, offsets, smooth_old, smooth_new, test_probs, win);
   }
@@ -250,7 +240,7 @@ extern "C" int pasnl_scene_labels(long m, const int* proj, const float* probs, i
   PASNL_REQUIRE(nl <= SL_MAXL, PASNL_EUNSUPPORTED);
   if (m == 0) return PASNL_OK;
   PASNL_REQUIRE(probs && label_values && ignored && out_preds && (potentials || !out_pots), PASNL_ENULL);
-  hipLaunchKernelGGL(scene_labels_kernel, dim3(sc_blocks(m, 256)), dim3(256), 0, pasnl_hip_stream(stream), m, proj, probs, nc,
+  hipLaunchKernelGGL(scene_labels_kernel, dim3(wt_blocks(m, 256)), dim3(256), 0, pasnl_hip_stream(stream), m, proj, probs, nc,
                      potentials, label_values, ignored, nl, out_preds, out_pots, out_probs);
   return pasnl_launch_status();
 }
@@ -261,7 +251,7 @@ extern "C" int pasnl_confusion_matrix(long n, const int* targets, const int* pre
   PASNL_REQUIRE(nl <= CM_MAXL, PASNL_EUNSUPPORTED);
   if (n == 0) return PASNL_OK;
   PASNL_REQUIRE(targets && preds && label_values && out, PASNL_ENULL);
-  const unsigned blocks = sc_blocks(n, 256 * 16);
+  const unsigned blocks = wt_blocks(n, 256 * 16);
   hipLaunchKernelGGL(confusion_kernel, dim3(blocks < (unsigned)CM_BLOCKS ? blocks : (unsigned)CM_BLOCKS), dim3(256),
                      (size_t)(nl * nl + nl) * 4, pasnl_hip_stream(stream), n, targets, preds, label_values, nl,
                      reinterpret_cast<unsigned long long*>(out));

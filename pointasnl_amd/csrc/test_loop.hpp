@@ -1,5 +1,6 @@
 // Device pieces the two test loops share (scan_test.hip: SemanticKITTI; scene_test.hip and the fused pick of crop.hip:
-// ScanNet): numpy's argmin and min on float64, the LDS sort of a crop's (d2, position) pairs, a NaN-propagating max.
+// ScanNet): numpy's argmin and min on float64, the LDS sort of a crop's (d2, position) pairs, a NaN-propagating max, the
+// winner mark and the float32 softmax of a crop's votes.
 #pragma once
 #include "common.hpp"
 
@@ -81,6 +82,21 @@ __device__ __forceinline__ T st_chain3(T acc, const T* tile, int cnt, int col) {
   }
   for (; k < cnt; ++k) acc = acc + tile[k * 3 + col];
   return acc;
+}
+
+// ---- votes of a crop: of the rows that select the same point the last one wins; win[] holds -1 between crops
+static __global__ __launch_bounds__(256) void vote_mark_kernel(int num_point, const int* __restrict__ select, int* __restrict__ win) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < num_point) atomicMax(&win[select[j]], j);
+}
+
+// tf.nn.softmax of one row in float32: max, exp(x - max), their sum in index order, the division
+__device__ __forceinline__ void vote_softmax(const float* __restrict__ v, int nc, float* p) {
+  float m = v[0];
+  for (int q = 1; q < nc; ++q) m = v[q] > m ? v[q] : m;
+  float s = 0.0f;
+  for (int q = 0; q < nc; ++q) { p[q] = expf(v[q] - m); s += p[q]; }
+  for (int q = 0; q < nc; ++q) p[q] = p[q] / s;
 }
 
 // ---- order / permute: bitonic sort of (d2 bits, position) in LDS.  The flipped-merge form sorts any count m without padding:

@@ -8,7 +8,7 @@
 //
 // What stays on the host: the numpy RNG stream (choices, shifts, the blocks' shuffles) and the merge of small blocks, which
 // works on per-window counts and centres only.  One vote of one scene is
-//   pasnl_window_noise (2 launches) -> pasnl_window_bounds (1) -> [six floats down] -> pasnl_window_count (2) ->
+//   pasnl_window_noise (2 launches) -> pasnl_window_bounds (1) -> [six floats down] -> pasnl_window_count (clear + 2) ->
 //   [W counts down; merge; permutations up] -> pasnl_window_fill (1) -> per batch: pasnl_window_gather, forward,
 //   pasnl_window_vote with no synchronisation in between.
 #include <math.h>
@@ -136,92 +136,9 @@ __global__ __launch_bounds__(ST_THREADS) void window_bounds_kernel(long n, const
   }
 }
 
-// ---- windows (D:223-242)
-constexpr int WW_MAX = 64;     // windows per axis: a point's memberships along an axis are one 64-bit mask
-constexpr int WW_WAVES = 4;    // chunks (of 64 consecutive points, one wave each) per workgroup
-
-// Which windows hold point p, axis by axis.  The comparisons are the reference's own: the float32 coordinate against the
-// float64 bound curmin - 0.2 / curmax + 0.2 (in20) and curmin - 0.001 / curmax + 0.001 (in1), with
-// curmin = float64(coordmin) + i * delta and curmax = curmin + 1.5 -- every window of the axis is tested, no index is derived
-// from a division.  z: curmin = coordmin_z + 0, curmax = curmin + float64(float32(coordmax_z - coordmin_z)).
-struct WinMember {
-  unsigned long long x20, y20, x1, y1;
-  bool z20, z1;
-};
-
-__device__ __forceinline__ void axis_masks(double p, double origin, int count, double delta, unsigned long long& m20,
-                                           unsigned long long& m1) {
-  m20 = 0ull;
-  m1 = 0ull;
-  for (int i = 0; i < count; ++i) {
-    const double curmin = origin + (double)i * delta;
-    const double curmax = curmin + 1.5;
-    if (p >= curmin - 0.2 && p <= curmax + 0.2) m20 |= 1ull << i;
-    if (p >= curmin - 0.001 && p <= curmax + 0.001) m1 |= 1ull << i;
-  }
-}
-
-__device__ __forceinline__ WinMember win_member(const float* __restrict__ p, const float* __restrict__ b, int nx, int ny, double delta) {
-  WinMember m;
-  axis_masks((double)p[0], (double)b[0], nx, delta, m.x20, m.x1);
-  axis_masks((double)p[1], (double)b[1], ny, delta, m.y20, m.y1);
-  const double pz = (double)p[2];
-  const double zmin = (double)b[2] + 0.0;
-  const double zmax = zmin + (double)(b[5] - b[2]);
-  m.z20 = pz >= zmin - 0.2 && pz <= zmax + 0.2;
-  m.z1 = pz >= zmin - 0.001 && pz <= zmax + 0.001;
-  return m;
-}
-
-// pass 1: hist[w][chunk] = members of window w among the chunk's 64 points (a ballot: no atomics at all)
-__global__ __launch_bounds__(64 * WW_WAVES) void window_count_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
-                                                                     int nx, int ny, double delta, long nchunks, int* __restrict__ hist) {
-  const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * WW_WAVES + (threadIdx.x >> 6);
-  if (c >= nchunks) return;  // whole waves leave
-  const long p = c * 64 + lane;
-  WinMember m = {0ull, 0ull, 0ull, 0ull, false, false};
-  if (p < n) m = win_member(xyz + p * 3, bounds, nx, ny, delta);
-  for (int i = 0; i < nx; ++i) {
-    const bool fx = m.z20 && ((m.x20 >> i) & 1ull);
-    for (int j = 0; j < ny; ++j) {
-      const unsigned long long ballot = __ballot(fx && ((m.y20 >> j) & 1ull));
-      if (lane == 0) hist[(size_t)(i * ny + j) * nchunks + c] = __popcll(ballot);
-    }
-  }
-}
-
-// pass 2 is window_scan_kernel (window_scan.hpp): per window an exclusive scan over the chunks, in place
-
-// pass 3: a member's place is woff[w] + (members in earlier chunks) + (members among the lower lanes): ascending scene index
-__global__ __launch_bounds__(64 * WW_WAVES) void window_fill_kernel(long n, const float* __restrict__ xyz, const float* __restrict__ bounds,
-                                                                    int nx, int ny, double delta, long nchunks, const int* __restrict__ hist,
-                                                                    const int* __restrict__ woff, long cap, int* __restrict__ out_idx,
-                                                                    unsigned char* __restrict__ out_mask) {
-  const int lane = threadIdx.x & 63;
-  const long c = (long)blockIdx.x * WW_WAVES + (threadIdx.x >> 6);
-  if (c >= nchunks) return;
-  const long p = c * 64 + lane;
-  WinMember m = {0ull, 0ull, 0ull, 0ull, false, false};
-  if (p < n) m = win_member(xyz + p * 3, bounds, nx, ny, delta);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int i = 0; i < nx; ++i) {
-    const bool fx = m.z20 && ((m.x20 >> i) & 1ull);
-    for (int j = 0; j < ny; ++j) {
-      const bool in = fx && ((m.y20 >> j) & 1ull);
-      const unsigned long long ballot = __ballot(in);
-      const int w = i * ny + j;
-      if (in) {
-        const int off = woff[w];
-        const long pos = (long)off + hist[(size_t)w * nchunks + c] + __popcll(ballot & below);
-        if (off >= 0 && pos < cap) {  // (the host sizes the lists from the counts: always taken)
-          out_idx[pos] = (int)p;
-          out_mask[pos] = (m.z1 && ((m.x1 >> i) & 1ull) && ((m.y1 >> j) & 1ull)) ? 1 : 0;
-        }
-      }
-    }
-  }
-}
+// ---- windows (D:223-242): curmin = float64(coordmin) + i * delta, curmax = curmin + 1.5, membership inside 0.2 and the mask
+// inside 0.001 -- window_scan.hpp's three passes over this grid
+static inline ColumnGrid window_grid(int nx, int ny, double delta) { return {nx, ny, delta, 1.5, false, 0.2, 0.001}; }
 
 // ---- rows (D:271-300): one thread per row entry
 __global__ __launch_bounds__(256) void window_gather_kernel(long entries, long real_entries, const int* __restrict__ rowpos, long cap,
@@ -300,33 +217,22 @@ extern "C" int pasnl_window_bounds(long n, const float* xyz, float* out_bounds, 
   return pasnl_launch_status();
 }
 
-extern "C" size_t pasnl_window_hist_bytes(long n, int nx, int ny) {
-  if (n <= 0 || nx <= 0 || ny <= 0) return 0;
-  return (size_t)nx * (size_t)ny * (size_t)wt_chunks(n) * sizeof(int);
-}
+extern "C" size_t pasnl_window_hist_bytes(long n, int nx, int ny) { return wt_hist_bytes(n, nx, ny); }
 
 extern "C" int pasnl_window_count(long n, const float* xyz, const float* bounds, int nx, int ny, double delta, int* hist, int* out_counts,
                                   pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0 && delta > 0.0, PASNL_EINVAL);
-  PASNL_REQUIRE(nx <= WW_MAX && ny <= WW_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(wt_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
   PASNL_REQUIRE(xyz && bounds && hist && out_counts, PASNL_ENULL);
-  hipStream_t s = pasnl_hip_stream(stream);
-  const long nchunks = wt_chunks(n);
-  hipLaunchKernelGGL(window_count_kernel, dim3(wt_blocks(nchunks, WW_WAVES)), dim3(64 * WW_WAVES), 0, s, n, xyz, bounds, nx, ny, delta,
-                     nchunks, hist);
-  hipLaunchKernelGGL(window_scan_kernel, dim3(nx * ny), dim3(256), 0, s, nchunks, hist, out_counts);
-  return pasnl_launch_status();
+  return wt_count(n, xyz, bounds, window_grid(nx, ny, delta), hist, out_counts, pasnl_hip_stream(stream));
 }
 
 extern "C" int pasnl_window_fill(long n, const float* xyz, const float* bounds, int nx, int ny, double delta, const int* hist,
                                  const int* woff, long cap, int* out_idx, unsigned char* out_mask, pasnl_stream_t stream) {
   PASNL_REQUIRE(n > 0 && n <= (1L << 30) && nx > 0 && ny > 0 && delta > 0.0 && cap > 0, PASNL_EINVAL);
-  PASNL_REQUIRE(nx <= WW_MAX && ny <= WW_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(wt_grid_ok(nx, ny), PASNL_EUNSUPPORTED);
   PASNL_REQUIRE(xyz && bounds && hist && woff && out_idx && out_mask, PASNL_ENULL);
-  const long nchunks = wt_chunks(n);
-  hipLaunchKernelGGL(window_fill_kernel, dim3(wt_blocks(nchunks, WW_WAVES)), dim3(64 * WW_WAVES), 0, pasnl_hip_stream(stream), n, xyz,
-                     bounds, nx, ny, delta, nchunks, hist, woff, cap, out_idx, out_mask);
-  return pasnl_launch_status();
+  return wt_fill(n, xyz, bounds, window_grid(nx, ny, delta), -1, 0.0, hist, woff, cap, out_idx, out_mask, pasnl_hip_stream(stream));
 }
 
 extern "C" int pasnl_window_gather(int rows, int real_rows, int block_points, const int* rowpos, long cap, const int* cat_idx,

@@ -443,3 +443,67 @@ def test_drop_in_dataset_classes(gold, scenes, kind):
                 assert got.dtype == want.dtype and got.shape == want.shape
                 np.testing.assert_array_equal(bits(got), bits(want))
             np.testing.assert_array_equal(state_of(rng), gold["%s/%d/rng" % (tag, visit)])
+
+
+def spread(seed, n, extent):
+    """n points uniform over `extent` metres from (-1.0, 0.3, 0.1), and labels -> (n,3) f32, (n,) i64"""
+    rng = np.random.default_rng(seed)
+    return (rng.random((n, 3)) * extent + [-1.0, 0.3, 0.1]).astype(np.float32), rng.integers(0, C, n)
+
+
+def same_columns(T, t, xyz, hist, counts):
+    """the grid's counts and, through pasnl_block_fill, its lists and masks against the restatement's"""
+    shape, rcounts, found = R.columns(xyz)
+    np.testing.assert_array_equal(counts, rcounts)
+    idx, mask = device_lists(T, t.xyz[0], t.bounds[0], -1, shape[0], shape[1], hist, counts)
+    np.testing.assert_array_equal(idx, np.concatenate([m for _, m, _ in found]))
+    np.testing.assert_array_equal(mask.astype(bool), np.concatenate([m for _, _, m in found]))
+    return shape, found
+
+
+@pytest.mark.parametrize("n", [2, 63, 64, 65, 257])
+def test_crop_and_grid_at_every_chunking(T, n):
+    """D:42-55 and D:98-115 with a two-lane wave (the smallest scene that has a grid), a wave one short of full, a full
+    one, one point past the wave boundary, and five chunks (two workgroups of four): the try's statistics, the chopped
+    column's list and 0.01 mask, and the grid's counts, lists and 0.001 masks are the restatement's.  One point has zero
+    extent and raises as it always did."""
+    xyz, labels = spread(80 + n, n, (4.0, 2.6, 2.2))
+    one = T.BlockTester([xyz[:1]], [labels[:1]], num_classes=C, block_points=P, batch_size=B)
+    with pytest.raises(ValueError, match="zero z extent"):
+        one.crop_stats(0, 0)
+    with pytest.raises(ValueError, match="zero extent"):
+        one.column_counts(0)
+    t = T.BlockTester([xyz], [labels], num_classes=C, block_points=P, batch_size=B)
+    coordmin, coordmax = R.bounds(xyz)
+    for centre in sorted({0, n // 2, n - 1}):
+        want = R.crop_stats(xyz, labels, xyz[centre], coordmin[2], coordmax[2])
+        m, labelled, nuniq, hist = t.crop_stats(0, centre)
+        assert (m, labelled, nuniq) == (want["m"], want["labelled"], want["nuniq"]) and centre in want["members"]
+        idx, mask = device_lists(T, t.xyz[0], t.bounds[0], centre, 1, 1, hist, np.array([m]))
+        np.testing.assert_array_equal(idx, want["members"])
+        np.testing.assert_array_equal(mask.astype(bool), want["mask"])
+    shape, counts, hist = t.column_counts(0)
+    assert same_columns(T, t, xyz, hist, counts)[0] == shape and (n < 63 or shape == (3, 2))
+
+
+def test_more_than_64_columns_per_axis(T):
+    """300 points over 100 m x 2 m: 66 or more columns of 1.5 m in x, which the 64-bit masks of the earlier kernels
+    refused; most columns are empty for any one wave.  Counts, lists, masks and the rows are the restatement's; and the
+    count kernel stores only non-zero counts, so the entry point must clear a stale histogram itself."""
+    from pointasnl_amd import _hip
+
+    n = 300
+    xyz, labels = spread(91, n, (100.0, 2.0, 2.2))
+    ref_rng, rng = np.random.RandomState(91), np.random.RandomState(91)
+    t = T.BlockTester([xyz], [labels], num_classes=C, block_points=P, batch_size=B, labelweights=WEIGHTS, rng=rng)
+    shape, counts, hist = t.column_counts(0)  # (raises PasnlUnsupported if the limit came back)
+    assert shape[0] > 64
+    _, found = same_columns(T, t, xyz, hist, counts)
+    assert any((np.bincount(m // 64, minlength=5) == 0).any() for _, m, _ in found)  # cells no wave ever stores
+    same_item(t.scene_blocks(0), R.whole_item(xyz, labels, WEIGHTS, P, ref_rng, with_rgb=False)[:3])
+    np.testing.assert_array_equal(state_of(rng), state_of(ref_rng))
+    stale = torch.full_like(hist, 0x7f7f7f7f)
+    cnt = torch.full((shape[0] * shape[1],), -1, dtype=torch.int32, device="cuda")
+    _hip.launch("pasnl_block_grid_count", "count", ctypes.c_long(n), ptr(t.xyz[0]), ptr(t.bounds[0]), shape[0], shape[1], ptr(stale), ptr(cnt))
+    np.testing.assert_array_equal(host(cnt), counts)
+    same_columns(T, t, xyz, stale, counts)

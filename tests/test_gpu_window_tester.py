@@ -280,3 +280,45 @@ def test_pool_argmax_takes_the_first_maximum_and_zero_without_a_vote():
     _hip.launch("pasnl_window_pool_labels", "labels", ctypes.c_long(5000), C, ctypes.c_void_p(pd.data_ptr()), ctypes.c_void_p(out.data_ptr()))
     np.testing.assert_array_equal(host(out), np.argmax(pool.astype(np.float64), 1))
     assert host(out)[:100].max() == 0 and (host(out)[100:200] == 4).all()
+
+
+def spread(seed, n, extent):
+    """n points uniform over `extent` metres, with colours -> (n,6) f32"""
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(np.hstack([rng.random((n, 3)) * extent, rng.random((n, 3))]).astype(np.float32))
+
+
+@pytest.mark.parametrize("n", [2, 63, 64, 65, 257])
+def test_windows_at_every_chunking(W, n):
+    """D:214-242 with a two-lane wave (the smallest scene that has a grid), a wave one short of full, a full
+    one, one point past the wave boundary, and five chunks (two workgroups of four): counts, lists and masks are the
+    restatement's.  One point has zero extent and raises as it always did."""
+    pts = spread(70 + n, n, (2.6, 2.1, 1.5))
+    with pytest.raises(ValueError, match="zero extent"):
+        W.WindowTester([pts[:1]], labels=[labels_of(n, 1)], noise_ratio=0.0, rng=np.random.RandomState(n)).window_lists(0)
+    t = W.WindowTester([pts], labels=[labels_of(n, n)], noise_ratio=0.0, rng=np.random.RandomState(n))
+    counts, found = check_windows(t, 0, pts[:, 0:3])
+    assert counts.sum() > n and len(found) >= 2  # windows overlap: a point is listed more than once
+
+
+def test_more_than_64_windows_per_axis(W):
+    """300 points over 34 m x 2 m at stride 0.5: 66 or more windows in x, which the 64-bit masks of the earlier kernels
+    refused; most windows are empty for any one wave.  Lists and masks are the restatement's; and the count kernel stores
+    only non-zero counts, so the entry point must clear a stale histogram itself."""
+    import ctypes
+
+    from pointasnl_amd import _hip
+
+    n = 300
+    pts = spread(81, n, (34.0, 2.0, 1.5))
+    t = W.WindowTester([pts], labels=[labels_of(81, n)], noise_ratio=0.0, rng=np.random.RandomState(81))
+    _, _, nx, ny = t.grid(0)
+    assert nx > 64
+    counts, found = check_windows(t, 0, pts[:, 0:3])  # (raises PasnlUnsupported if the limit came back)
+    per_chunk = [np.bincount(m // 64, minlength=5) for _, m, _, _ in found]
+    assert any((c == 0).any() for c in per_chunk)  # windows that are empty for some chunks: their cells are never stored
+    hist = torch.full((int(_hip.lib().pasnl_window_hist_bytes(ctypes.c_long(n), nx, ny)) // 4,), 0x7f7f7f7f, dtype=torch.int32, device="cuda")
+    cnt = torch.full((nx * ny,), -1, dtype=torch.int32, device="cuda")
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    _hip.launch("pasnl_window_count", "count", ctypes.c_long(n), p(t.xyz[0]), p(t.bounds), nx, ny, ctypes.c_double(0.5), p(hist), p(cnt))
+    np.testing.assert_array_equal(host(cnt), counts)

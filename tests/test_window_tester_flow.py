@@ -205,7 +205,10 @@ def test_window_entries_are_declared_exported_and_importable():
     assert lib.pasnl_version() == 100
     assert lib.pasnl_window_hist_bytes(ctypes.c_long(200000), 13, 11) == 13 * 11 * 3125 * 4
     null = ctypes.c_void_p(0)
-    assert lib.pasnl_window_count(ctypes.c_long(100), null, null, 65, 3, ctypes.c_double(0.5), null, null, null) == -5  # > 64 per axis
+    assert lib.pasnl_window_hist_bytes(ctypes.c_long(120000), 73, 73) == 73 * 73 * 1875 * 4  # no limit of 64 per axis
+    assert lib.pasnl_window_hist_bytes(ctypes.c_long(120000), 50000, 50000) == 0                # positions past int32
+    assert lib.pasnl_window_count(ctypes.c_long(100), null, null, 50000, 50000, ctypes.c_double(0.5), null, null, null) == -5
+    assert lib.pasnl_window_count(ctypes.c_long(100), null, null, 65, 3, ctypes.c_double(0.5), null, null, null) == -2  # > 64 per axis
     assert lib.pasnl_window_count(ctypes.c_long(100), null, null, 4, 3, ctypes.c_double(0.5), null, null, null) == -2
     assert lib.pasnl_window_vote(1, 8, 1, null, null, null, ctypes.c_long(5), null, null) == -1            # c < 2
     assert lib.pasnl_window_gather(0, 0, 8, null, ctypes.c_long(1), null, null, ctypes.c_long(5), null, null, 0, null, null, 1, null, null,
