@@ -7,7 +7,10 @@
  *
  *   - all tensors are contiguous row-major, float32 / int32 (int64 only where stated);
  *   - pointers are DEVICE pointers owned by the caller (the Python host hands in torch storage);
- *     inputs are borrowed const, outputs are fully overwritten;
+ *     inputs are borrowed const, outputs are fully overwritten -- exactly the elements of the stated shape, never a byte
+ *     beside them (rows and tiles are stored masked), and a workspace is used up to the bytes its size function returns and
+ *     no further (tests/test_gpu_abi_bounds.py); where part of an output is NOT written or its contents are unspecified, the
+ *     entry says so;
  *   - work is enqueued asynchronously on `stream` (a hipStream_t passed as void*; NULL = the null
  *     stream); no implicit synchronisation, no allocation, no global state -> graph-capturable and
  *     thread-safe;
@@ -59,11 +62,12 @@ int pasnl_farthest_point_sample(int b, int n, int m, const float* xyz, int* idx,
 /* The same sampling, and the gather of the sampled coordinates in the same launch: new_xyz[b,j,:] = xyz[b, idx[b,j], :]
  * (bit-equal to pasnl_gather_point on idx).  Replaces the pair farthest_point_sample + gather_point every caller of the
  * reference runs back to back (pointasnl_util.py:33-49 sampling(), pointnet_util.py:44): the sampler has the picks in
- * LDS when it ends, so the second launch -- on the critical path of every set-abstraction layer -- disappears. */
+ * LDS when it ends, so the second launch -- on the critical path of every set-abstraction layer -- disappears.
+ * idx (b,m) i32, new_xyz (b,m,3) f32. */
 int pasnl_farthest_point_sample_gather(int b, int n, int m, const float* xyz, int* idx, float* new_xyz,
                                        pasnl_stream_t stream);
 
-/* out[b,j,:] = inp[b, idx[b,j], :] for 3-wide rows.
+/* out[b,j,:] = inp[b, idx[b,j], :] for 3-wide rows: inp (b,n,3), idx (b,m) i32 -> out (b,m,3).
  * replaces gatherpointLauncher  tf_sampling_g.cu:206-208 (kernel :172-181) */
 int pasnl_gather_point(int b, int n, int m, const float* inp, const int* idx, float* out, pasnl_stream_t stream);
 
@@ -72,7 +76,9 @@ int pasnl_gather_point(int b, int n, int m, const float* inp, const int* idx, fl
 int pasnl_gather_point_grad(int b, int n, int m, const float* out_g, const int* idx, float* inp_g, pasnl_stream_t stream);
 
 /* Inverse-CDF sampling: out[b,j] = first r with cdf[b,r] >= inpr[b,j]*cdf[b,n-1]; `temp` (b*n floats)
- * receives the running sum.  replaces probsampleLauncher  tf_sampling_g.cu:198-201 (:7-104) */
+ * receives the running sum.  replaces probsampleLauncher  tf_sampling_g.cu:198-201 (:7-104)
+ * inp_p (b,n), inp_r (b,m) -> out (b,m) i32.  temp is scratch: all b*n floats may be written, its contents afterwards are
+ * UNSPECIFIED (the sums are formed in another order than a sequential loop's). */
 int pasnl_prob_sample(int b, int n, int m, const float* inp_p, const float* inp_r, float* temp, int* out, pasnl_stream_t stream);
 
 /* ------------------------------------------------------------------ grouping (tf_ops/grouping) */
@@ -84,7 +90,7 @@ int pasnl_prob_sample(int b, int n, int m, const float* inp_p, const float* inp_
 int pasnl_query_ball_point(int b, int n, int m, float radius, int nsample, const float* xyz1, const float* xyz2,
                            int* idx, int* pts_cnt, pasnl_stream_t stream);
 
-/* out[b,j,k,:] = points[b, idx[b,j,k], :], row length c.
+/* out[b,j,k,:] = points[b, idx[b,j,k], :], row length c: points (b,n,c), idx (b,m,nsample) i32 -> out (b,m,nsample,c).
  * replaces groupPointLauncher  tf_grouping_g.cu:133-134 (kernel :40-57).  With nsample == 1 this is the
  * C-wide row gather the models do through tf.gather_nd (pointasnl_util.py:43-49,63-71). */
 int pasnl_group_point(int b, int n, int c, int m, int nsample, const float* points, const int* idx, float* out,
@@ -195,7 +201,8 @@ int pasnl_three_nn(int b, int n, int m, const float* xyz1, const float* xyz2, fl
                    pasnl_stream_t stream);
 
 /* out[b,j,l] = (p[i1,l]*w1 + p[i2,l]*w2) + p[i3,l]*w3.
- * replaces threeinterpolate_cpu  tf_interpolate.cpp:107-127   (note the argument order b,m,c,n) */
+ * replaces threeinterpolate_cpu  tf_interpolate.cpp:107-127   (note the argument order b,m,c,n)
+ * points (b,m,c), idx (b,n,3) i32, weight (b,n,3) -> out (b,n,c) */
 int pasnl_three_interpolate(int b, int m, int c, int n, const float* points, const int* idx, const float* weight,
                             float* out, pasnl_stream_t stream);
 
@@ -242,14 +249,16 @@ int pasnl_nl_attention_ws(int b, int p, int n, int cb, const float* q, const flo
 /* Adaptive-Sampling micro self-attention over the first `as` neighbours of each query
  * (SampleWeights, pointasnl_util.py:136-146):  g groups, each q,k,v (as,cb):
  *   out[g,i,:] = softmax_j( q[g,i,:] . k[g,j,:] / sqrt(cb) ) . v[g,j,:]
- * q (g,as,cb); kv (g,as,2*cb) (K first, V second, :133-134); out (g,as,cb).  as <= 16, cb <= 256. */
+ * q (g,as,cb); kv (g,as,2*cb) (K first, V second, :133-134); out (g,as,cb).  as <= 16, cb <= 256.
+ * (pasnl_as_attention_qkv and pasnl_as_attention_proj below: the same out (g,as,cb).) */
 int pasnl_as_attention(int g, int as, int cb, const float* q, const float* kv, float* out, pasnl_stream_t stream);
 
 /* AdaptiveSampling tail (pointasnl_util.py:154-155,167-171): softmax over the neighbour axis of
  * logits (g,as,1+ch), then new_xyz[g,:] = sum_k w[g,k,0]*xyz[g,k,:] and
  * new_feature[g,c] = sum_k w[g,k,1+c]*feat[g,k,c].
  * xyz rows are taken from grouped_xyz (g,nsample,3) and feat from grouped_feature (g,nsample,ch):
- * only the first `as` of `nsample` neighbours are read (the :165-166 slices). */
+ * only the first `as` of `nsample` neighbours are read (the :165-166 slices).
+ * -> new_xyz (g,3), new_feature (g,ch); the same two outputs for pasnl_as_reweight_x and the pasnl_as_cell_* entries below. */
 int pasnl_as_reweight(int g, int as, int nsample, int ch, const float* logits, const float* grouped_xyz,
                       const float* grouped_feature, float* new_xyz, float* new_feature, pasnl_stream_t stream);
 
@@ -315,7 +324,9 @@ int pasnl_sa_cell_pre_centre0(int b, int n, int c, int m, int k, int c1, int c2,
  * operand order -- pasnl_mlp3_pack_weights(c, c1, w0 + 6 * c1, w0_features_packed) and pasnl_mlp3_pack_weights(c1, c2, w1,
  * w1_packed), once per variable -- for the kernels that stream their weights from L2 (one workgroup per group: c1 = c2 in
  * {256, 512}, and 128 with few groups or one convolution): 16-byte weight loads.  The row-major matrices are still required
- * (the first rows of w0, every other kernel); NULL packed pointers = the plain entry points; identical results. */
+ * (the first rows of w0, every other kernel); NULL packed pointers = the plain entry points; identical results.
+ * out (b*npoint, c2*32), skip_max (b,npoint,6+c); new_xyz_out (b,npoint,3) and new_feature_out (b,npoint,3+c) are NOT written
+ * when new_xyz is given (they may be NULL then). */
 int pasnl_sa_cell_packed(int b, int n, int c, int npoint, int nsample, int c1, int c2, const float* xyz, const float* feature,
                          const int* idx, const float* new_xyz, const float* w0, const float* b0, const float* w1, const float* b1,
                          const float* ww, const float* bw, const float* w0_features_packed, const float* w1_packed, float* out,
@@ -326,7 +337,9 @@ int pasnl_sa_cell_packed(int b, int n, int c, int npoint, int nsample, int c1, i
 int pasnl_max_pool_rows(int b, int n, int c, const float* x, float* out, pasnl_stream_t stream);
 
 /* The same pooling into rows of a wider table: out[b * out_stride + ch], out_stride >= c -- the two pooled vectors of
- * pointasnl_cls land side by side in the (B, 1536) input of fc1 (models/pointasnl_cls.py:43-45: the tf.concat is free). */
+ * pointasnl_cls land side by side in the (B, 1536) input of fc1 (models/pointasnl_cls.py:43-45: the tf.concat is free).
+ * Only the c floats at out + row * out_stride are written: the other columns of the table are NOT written (the last row
+ * needs c floats, not out_stride). */
 int pasnl_max_pool_rows_strided(int b, int n, int c, const float* x, float* out, long out_stride, pasnl_stream_t stream);
 
 /* The "group all" set-abstraction module in one kernel (csrc/mlp_pool.hip): pointnet_sa_module(..., group_all=True) of
@@ -338,7 +351,8 @@ int pasnl_max_pool_rows_strided(int b, int n, int c, const float* x, float* out,
  * operand order -- pasnl_mlp3_pack_weights(k, n, w, packed) once per variable into pasnl_mlp3_packed_weights_bytes(k, n) bytes
  * (16-byte aligned): packed[((bt * 2 + h) * n + col) * 8 + u] = w[16 bt + 2 u + h][col], zero beyond k.  Covered: (c1,c2,c3) =
  * (128,256,512) and (256,512,1024), k0 % 4 == 0, x 16-byte aligned; otherwise PASNL_EUNSUPPORTED (the caller runs the layers
- * one by one).  workspace: pasnl_mlp3_max_pool_workspace_bytes(b, n, c3) bytes (maxima per tile of 32 points; no need to clear it). */
+ * one by one).  workspace: pasnl_mlp3_max_pool_workspace_bytes(b, n, c3) bytes (maxima per tile of 32 points; no need to clear it).
+ * out: c3 floats per cloud at out + cloud * out_stride, out_stride >= c3; the other columns of the table are NOT written. */
 size_t pasnl_mlp3_packed_weights_bytes(int k, int n);
 int pasnl_mlp3_pack_weights(int k, int n, const float* w, float* packed, pasnl_stream_t stream);
 size_t pasnl_mlp3_max_pool_workspace_bytes(int b, int n, int c3);
@@ -352,8 +366,8 @@ int pasnl_mlp3_max_pool(int b, int n, int k0, int c1, int c2, int c3, const floa
  * [nsample x channel] window (utils/pointasnl_util.py:275, 337; tf_util.py:120-185).  Every fp32 operand is split into three
  * bf16 terms and the six products of weight >= 2^-16 are accumulated in fp32 on v_mfma_f32_32x32x16_bf16: about one more
  * rounding per product than an fp32 fmaf chain (inside the 1e-5 contract, not the same bits).
- *   pasnl_bf16x3_split_weights: w (kdim,n) fp32 -> wsplit (pasnl_bf16x3_weights_bytes(kdim, n) bytes, 16-byte aligned), once
- *   per layer; pasnl_dense_bf16x3: kdim % 32 == 0, n % 128 == 0, lda % 4 == 0, x 16-byte aligned, else PASNL_EUNSUPPORTED. */
+ *   pasnl_bf16x3_split_weights: w (kdim,n) fp32 -> wsplit (pasnl_bf16x3_weights_bytes(kdim, n) = 6 kdim n bytes, 16-byte
+ *   aligned: three bf16 planes hi, mid, lo in operand order, wsplit[plane][kdim / 8][n][kdim % 8]), once per layer; pasnl_dense_bf16x3: kdim % 32 == 0, n % 128 == 0, lda % 4 == 0, x 16-byte aligned, else PASNL_EUNSUPPORTED. */
 size_t pasnl_bf16x3_weights_bytes(int kdim, int n);
 int pasnl_bf16x3_split_weights(int kdim, int n, const float* w, void* wsplit, pasnl_stream_t stream);
 int pasnl_dense_bf16x3(int rows, int kdim, int n, int lda, const float* x, const void* wsplit, const float* bias, int relu,
@@ -366,7 +380,9 @@ int pasnl_dense_bf16x3(int rows, int kdim, int n, int lda, const float* x, const
  * into w / bias by the caller).  A product this thin is cut along n AND along kdim over ~128 workgroups; the K slices meet in
  * `workspace` and are summed in slice order (bit-reproducible).  kdim % 8 == 0 and x 16-byte aligned, else PASNL_EUNSUPPORTED.
  * workspace: pasnl_dense_rows_workspace_bytes(rows, kdim, n) bytes of device memory, ZERO-FILLED once by the caller before
- * its first use (the kernel leaves its counters at zero); one workspace serves one stream at a time. */
+ * its first use (the kernel leaves its counters at zero); one workspace serves one stream at a time.  The counters are the
+ * first 4 * ceil(n / 32) bytes rounded up to 256: only they have to be zero, the partial sums behind them need no
+ * initialisation. */
 size_t pasnl_dense_rows_workspace_bytes(int rows, int kdim, int n);
 int pasnl_dense_rows(int rows, int kdim, int n, const float* x, const float* w, const float* bias, int relu, float* out,
                      void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
@@ -410,8 +426,8 @@ int pasnl_three_interpolate_grad_det(int b, int n, int c, int m, const float* gr
  *   out = relu( ( after + relu(skip_max ws + bs) + relu(att wb + bb) ) wagg + bagg )
  * after (rows,c) = the after_conv output; skip_max (rows,w) = pasnl_sa_cell's skip maxima; att (rows,cb) = pasnl_nl_attention's
  * output (cb == 0 and att/wb/bb NULL for a layer without non-local cell); ws (w,c), wb (cb,c), wagg (c,c) and the biases are
- * the BN-folded `skip`, `conv_back_project`, `aggregation` layers.  c % 32 == 0 and c <= 512, else PASNL_EUNSUPPORTED (the
- * Python mirror then runs the three GEMMs and two adds). */
+ * the BN-folded `skip`, `conv_back_project`, `aggregation` layers; out (rows,c).  c % 32 == 0 and c <= 512, else
+ * PASNL_EUNSUPPORTED (the Python mirror then runs the three GEMMs and two adds). */
 int pasnl_sa_tail(int rows, int w, int cb, int c, const float* after, const float* skip_max, const float* att, const float* ws,
                   const float* bs, const float* wb, const float* bb, const float* wagg, const float* bagg, float* out,
                   pasnl_stream_t stream);
@@ -425,7 +441,8 @@ int pasnl_sa_tail_res(int rows, int w, int cb, int c, const float* after, const 
 /* pasnl_sa_tail / _res / _cat with the three weight matrices PACKED in the matrix instruction's operand order (the kernel then
  * reads them in 16-byte pieces: 3-5 us per launch): pasnl_sa_tail_pack_weights(k, c, w, packed) once per variable into
  * pasnl_sa_tail_packed_weights_bytes(k, c) bytes (16-byte aligned): packed[((chunk * 2 + h) * c + col) * 16 + t] =
- * w[32 chunk + 2 t + h][col], zero beyond k.  residual (rows,c) or NULL; out_cat + new_xyz or NULL (see pasnl_sa_tail_cat). */
+ * w[32 chunk + 2 t + h][col], zero beyond k.  residual (rows,c) or NULL; out_cat + new_xyz or NULL (see pasnl_sa_tail_cat).
+ * out (rows,c); out_cat (rows,c+4) when given. */
 size_t pasnl_sa_tail_packed_weights_bytes(int k, int c);
 int pasnl_sa_tail_pack_weights(int k, int c, const float* w, float* packed, pasnl_stream_t stream);
 int pasnl_sa_tail_packed(int rows, int w, int cb, int c, const float* after, const float* skip_max, const float* att,
@@ -506,7 +523,8 @@ int pasnl_as_reweight_x(int g, int as, int ch, const float* logits, const float*
  * one row per occupied voxel of edge sample_dl: barycentre, feature mean, majority label.  Voxel keys, fp32 sums in
  * input order and the barycentre / mean arithmetic follow the reference bit for bit; rows come out in ASCENDING VOXEL
  * KEY (the reference emits unordered_map iteration order) and a label tie goes to the smallest label (the reference:
- * first maximum in hash order).  Outputs are sized for n rows; out_count (device int) receives the number of voxels.
+ * first maximum in hash order).  Outputs are sized for n rows: out_points (n,3), out_features (n,fdim), out_classes (n,ldim)
+ * i32; out_count (device int) receives the number of voxels, and the rows past it are NOT written.
  * workspace: pasnl_grid_subsample_workspace_bytes(n) bytes of device memory.  No host synchronisation. */
 size_t pasnl_grid_subsample_workspace_bytes(long n);
 int pasnl_grid_subsample(long n, int fdim, int ldim, const float* points, const float* features, const int* classes,
@@ -523,7 +541,7 @@ int pasnl_grid_subsample(long n, int fdim, int ldim, const float* points, const 
  * for every crop) nearest, clamped to [0, min(n, kcap)].
  * -> out_idx (b,kcap) i32: the selected indices in ASCENDING INDEX order (crop_pc shuffles them at once, :274; sort by
  * out_d2 for KDTree.query's order), entries behind the count are not written; out_d2 (b,kcap) f64 their squared
- * distances (NULL: not wanted); out_count (b) i32: the number selected (radius form: the TRUE number within the radius,
+ * distances (NULL: not wanted), entries behind the count not written either; out_count (b) i32: the number selected (radius form: the TRUE number within the radius,
  * which may exceed kcap -- only the first kcap by index are stored).
  * An exact radix selection on the 63 key bits (no tree), 8 launches, no host synchronisation.
  * workspace: pasnl_knn_crop_workspace_bytes(b, n) bytes (8 n per crop for the keys + histograms). */

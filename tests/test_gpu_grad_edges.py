@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import grad_edge_cases as E
+from guarded import GUARD, NAN_BYTE, WS_BYTE, Guarded  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -97,34 +98,6 @@ def lib_workspace_bytes(b, targets, entries):
     from pointasnl_amd import _hip
 
     return int(_hip.lib().pasnl_grad_workspace_bytes(int(b), int(targets), ctypes.c_long(int(entries))))
-
-
-GUARD = 256  # bytes on either side of a view (keeps the view's alignment)
-
-
-class Guarded:
-    """`nbytes` bytes inside a larger device buffer that is pre-filled with one byte value"""
-
-    def __init__(self, nbytes, fill):
-        self.nbytes, self.fill = nbytes, fill
-        self.buf = torch.full((GUARD + nbytes + GUARD,), fill, dtype=torch.uint8, device="cuda")
-        self.ptr = self.buf.data_ptr() + GUARD
-
-    def inside(self):
-        return self.buf[GUARD:GUARD + self.nbytes]
-
-    def floats(self, shape):
-        return self.inside().view(torch.float32).reshape(shape).cpu().numpy()
-
-    def guards_intact(self):
-        return bool((self.buf[:GUARD] == self.fill).all()) and bool((self.buf[GUARD + self.nbytes:] == self.fill).all())
-
-    def untouched(self):
-        return self.guards_intact() and bool((self.inside() == self.fill).all())
-
-
-NAN_BYTE = 0xFF   # four of them are a NaN
-WS_BYTE = 0xA5
 
 
 def run_abi(case, det=True, ws_bytes=None):
