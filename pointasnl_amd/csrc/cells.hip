@@ -1205,6 +1205,25 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       xs[4 * q] = t4.x; xs[4 * q + 1] = t4.y; xs[4 * q + 2] = t4.z; xs[4 * q + 3] = t4.w;
     }
   };
+  // PRE, during conv1's block cb: fold quarters [q0, q1) of the chunk the previous block requested (block 0: of chunk 0, which
+  // came with the tile's rows in xr) and request the same quarters of chunk 1 + cb of the row at feature offset off into xs
+  auto skip_quarters = [&](int cb, int q0, int q1, unsigned off) {
+    typedef __attribute__((address_space(3))) float lds_float;
+    lds_float* srow = (lds_float*)(skl + min(cb, nchunk - 1) * 32);
+    const int g0 = min(1 + cb, nchunk - 1) * 8 + 4 * h - 2;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q >= q0 && q < q1) {
+        // (a one-chunk row has nothing but chunk 0, whose first 8 columns exist in xr only: xs is not folded there)
+        if (cb == 0 || nchunk > 1) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            __hip_atomic_fetch_max(srow + 4 * q + e, cb == 0 ? xr[4 * q + e] : xs[4 * q + e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+        const float4 t4 = reinterpret_cast<const float4*>(fbase_ + off)[min(max(g0 + q, 0), cf4 - 1)];
+        xs[4 * q] = t4.x; xs[4 * q + 1] = t4.y; xs[4 * q + 2] = t4.z; xs[4 * q + 3] = t4.w;
+      }
+  };
   auto fold_skip = [&](int ch, const float (&v)[16]) {
     typedef __attribute__((address_space(3))) float lds_float;
     lds_float* srow = (lds_float*)(skl + ch * 32);
@@ -1253,9 +1272,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
 #pragma unroll
         for (int cb = 0; cb < C2 / 32; ++cb) asm volatile("" : "+a"(M[cb]));  // M lives in AccVGPRs: no VALU ever reads it
       }
-      // (this tile's rows were requested during the previous tile; now the indices of the following tile)
-      inext = src.idx[(tile + 32 < ktile ? (size_t)g * k + tile + 32 : (size_t)g_next * k) + ql];
-
       f32x16 H1T[C1 / 32];
       if constexpr (!PRE) {  // (PRE: the first conv0 step writes H1T from the gathered table rows)
 #pragma unroll
@@ -1280,14 +1296,18 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py), 0));
         cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pz), 0));
         if (src.new_feature_out) {  // neighbour 0's feature row: requested now, stored when the tile's matrix work has issued
-          const unsigned long long fp = reinterpret_cast<unsigned long long>(frow);
-          const float* f0 = reinterpret_cast<const float*>(
-              ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(fp >> 32), 0) << 32) |
-              (unsigned)__builtin_amdgcn_readlane((int)fp, 0));
+          // (lane 0's row offset on the kernel argument's pointer: a GLOBAL load.  A pointer rebuilt from two readlanes of its
+          // halves has no address space, the load becomes a flat one, and behind a flat load every vmcnt wait of the tile is a
+          // vmcnt(0) -- the top of the tile then waited for the index load issued a few instructions earlier, a full round trip
+          // per tile with nothing to hide it behind)
+          const float* f0 = fbase_ + (unsigned)__builtin_amdgcn_readlane((int)frow_off, 0);
           nf0 = f0[min(lane, cf - 1)];
           nf1 = f0[min(lane + 64, cf - 1)];
         }
       }
+      // (this tile's rows were requested during the previous tile; now the indices of the following tile.  The youngest load
+      // of the tile's prologue: the counted wait for the rows leaves it in flight)
+      inext = src.idx[(tile + 32 < ktile ? (size_t)g * k + tile + 32 : (size_t)g_next * k) + ql];
       const int nfull = wi >> 5;  // chunks whose 32 columns all exist
       if constexpr (XYZ3) {
         // internal columns 8..10 = the three features, 11..15 padding; step t holds columns 2t (h = 0) and 2t + 1 (h = 1)
@@ -1323,7 +1343,7 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
         for (int ob = 0; ob < C1 / 32; ++ob) H1T[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0c[0][ob], d0, pn[ob], 0, 0, 0);
 #pragma unroll
         for (int ob = 0; ob < C1 / 32; ++ob) H1T[ob] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0c[1][ob], d1, H1T[ob], 0, 0, 0);
-        fold_skip(0, xr);
+        // (chunk 0's skip maxima: folded behind conv1's first weight reads, see there)
       } else {  // (not re-indented: the plain form's conv0 over the whole row, chunk by chunk)
 
       constexpr int RS = VEC ? 1 : 2;  // W0 row / column stride between consecutive MFMA steps
@@ -1447,9 +1467,6 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
       } else
 #pragma unroll
       for (int cb = 0; cb < C2 / 32; ++cb) {
-        // PRE: chunk 1 + cb of this tile's rows for the skip maxima, folded behind the block's products (the last chunk again
-        // where the row has fewer: a maximum taken twice is the same maximum)
-        if constexpr (PRE) load_skip(min(1 + cb, nchunk - 1), fcur);
         f32x16 H2;
 #pragma unroll
         for (int r = 0; r < 16; ++r) H2[r] = 0.f;
@@ -1464,6 +1481,19 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
 #pragma unroll
               for (int t = 0; t < 16; ++t) wv[(blk + 1) & 1][t] = w1p[(size_t)((blk + 1) * 32 + kappa(t, 0)) * C2];
             }
+            if constexpr (PRE) {
+              // The skip maxima, one chunk of the tile's rows per block, a quarter of it (one 16-byte load) per weight batch:
+              // the quarter requested one block earlier (chunk 0 came with the tile's rows) is folded BEHIND the batch's
+              // weight reads and refilled in place with the same columns of the next chunk (the last chunk again where the row
+              // has fewer: a maximum taken twice is the same maximum).  The wave's LDS operations complete in order, at most 15
+              // can be outstanding, and a ds_max_f32 with 8 lanes per address is slow: with all 16 of a chunk issued at the end
+              // of a block, the next block's first product waited for most of them and for its own weights behind them, once
+              // per block with nothing to cover it (one wave per SIMD).  Four at a time drain under the batch's 16 products.
+              // A quarter's loads are a block older than its fold; block 1's are older than request_rows' 23.
+              static_assert(!PRE || C1 == 32 || C1 == 64 || C1 == 128, "a chunk's four quarters over 1, 2 or 4 weight batches");
+              constexpr int QB = 4 / (C1 / 32);
+              skip_quarters(cb, blk * QB, (blk + 1) * QB, fcur);
+            }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < 16; ++t) H2 = __builtin_amdgcn_mfma_f32_32x32x2f32(H1T[blk][t], wv[blk & 1][t], H2, 0, 0, 0);
@@ -1475,8 +1505,13 @@ __global__ __launch_bounds__(NW * 64) void sa_cell_kernel(long groups, int k, in
 #pragma unroll
         for (int t = 0; t < 16; ++t) M[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(H2[t], G[t], M[cb], 0, 0, 0);
         if constexpr (PRE) {
-          if (cb == 0) request_rows(tile + 32 < ktile ? bi : bi_next, inext);  // (see above: they arrive during blocks 1..)
-          if (nchunk > 1) fold_skip(min(1 + cb, nchunk - 1), xs);
+          if (cb == 0) {
+            // (opaque up to here: the row addresses' arithmetic -- the first use of the index -- otherwise moves up to conv0,
+            // and the wait for the index load with it)
+            asm volatile("" : "+v"(inext));
+            request_rows(tile + 32 < ktile ? bi : bi_next, inext);  // (see above: they arrive during blocks 1..)
+          }
+          if (cb == C2 / 32 - 1 && nchunk > 1) fold_skip(min(1 + cb, nchunk - 1), xs);  // (the chunk the last block requested)
         }
       }
       if constexpr (PRE) {
