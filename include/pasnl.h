@@ -837,6 +837,26 @@ int pasnl_modelnet_normalize(int s, int npoint, int ld, long n_shapes, const int
 int pasnl_modelnet_batch(int b, int bsize, int npoint, int ch, const int* order, long n_order, long start, long n_shapes,
                          const float* prepared, const int* shape_labels, float* batch, int* labels, pasnl_stream_t stream);
 
+/* The training loop's input side (train.py:224-241 with utils/provider.py (P) :39-253): next_batch fused with the whole
+ * augmentation chain, one launch.  For i < bsize and j < npoint, row (i, j) of batch (b,npoint,ch) f32 is computed from ONE row
+ * of prepared shape order[start + i], and labels[i] is that shape's class; rows bsize..b-1 of both are NOT touched (the short
+ * last batch keeps the augmented batch before it, train.py:214,240).  Only RNG draws come from the host: mats (bsize,2,9) f64,
+ * row-major, per cloud the rotation about y (P:61-66, 99-104) then R = Rz.Ry.Rx of the perturbation (P:120-130, 190-200), or
+ * NULL when rotation is off; scale (bsize) f64 (P:241); shift (bsize,3) f64 (P:227); perm (npoint) i32, the batch's one
+ * shuffled arange (P:47-49); ratio (bsize) f64 (P:249) and u (bsize,npoint) f64 (P:250).  The source row is perm[0] when
+ * u[i][j] <= ratio[i] (a tie drops) and perm[j] otherwise: the shuffle precedes the dropout, so P:252's first point is row
+ * perm[0] of the unshuffled cloud after every other step.  float64 arithmetic in train.py:226-237's order, every product
+ * (x0*M[0][c] + x1*M[1][c]) + x2*M[2][c]: ch = 6, rotation: float32((x @ A) @ R) for xyz and normal alike (P:107 stays float64,
+ * P:118 is float32); ch = 3, rotation: float32(float32(x @ A) @ R) (P:59 is float32); then on columns 0..2
+ * float32(float64(x) * scale) and float32(float64(that) + shift[c]) -- numpy >= 2's in-place float32 ops with float64
+ * operands.  Rotation off: float32((x * scale) + shift[c]) on columns 0..2, one rounding at the feed; normals are copied.
+ * A perm entry outside [0, npoint) or an order entry outside [0, n_shapes) leaves its rows unwritten.  bsize > b, start +
+ * bsize > n_order, npoint < 1 or ch not 3 or 6 -> PASNL_EINVAL. */
+int pasnl_modelnet_augment(int b, int bsize, int npoint, int ch, const int* order, long n_order, long start, long n_shapes,
+                           const float* prepared, const int* shape_labels, const double* mats, const double* scale,
+                           const double* shift, const int* perm, const double* ratio, const double* u, float* batch, int* labels,
+                           pasnl_stream_t stream);
+
 /* The noisy points (T:129-132 with normalize_data, P:8-24): uniforms (bsize,k,3) f64 as the host drew them; each (k,3) block
  * is normalised in float64 -- per column one sum down the rows / float64(k), subtracted, divided by
  * max(sqrt((x*x + y*y) + z*z)) -- rounded to float32 (the feed into a float32 placeholder) and written to rows 0..k-1,

@@ -9,7 +9,9 @@
 // shuffle of every vote).  One batch is
 //   [first visit, uniform: pasnl_modelnet_fps -> pasnl_modelnet_normalize] -> pasnl_modelnet_batch -> [pasnl_modelnet_noise]
 //   -> per vote: forward, pasnl_cls_vote -> pasnl_cls_tally
-// with no synchronisation in between; the counters come down once, at the end of the epoch.
+// with no synchronisation in between; the counters come down once, at the end of the epoch.  The training loop (train.py
+// :208-264) puts pasnl_modelnet_augment -- next_batch fused with the augmentation chain of utils/provider.py -- in the place of
+// pasnl_modelnet_batch and takes one vote.
 #include <math.h>
 #include "common.hpp"
 #include "test_loop.hpp"
@@ -126,6 +128,75 @@ __global__ __launch_bounds__(256) void modelnet_batch_kernel(long entries, int b
   if (e < bsize) {
     const long lid = order[e];
     if (lid >= 0 && lid < n_shapes) labels[e] = shape_labels[lid];
+  }
+}
+
+// ---- train.py:224-241 with P:39-253: next_batch and the whole augmentation chain, one thread per output point.  The draws
+// are the host's; every product and sum is numpy's float64 one, rounded to float32 where the reference's arrays are float32.
+__device__ __forceinline__ void ma_dot(const double x[3], const double* __restrict__ m, double out[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c] = (x[0] * m[c] + x[1] * m[3 + c]) + x[2] * m[6 + c];
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void modelnet_augment_kernel(long entries, int bsize, int npoint, const int* __restrict__ order,
+                                                               long n_shapes, const float* __restrict__ prepared,
+                                                               const int* __restrict__ shape_labels, const double* __restrict__ mats,
+                                                               const double* __restrict__ scale, const double* __restrict__ shift,
+                                                               const int* __restrict__ perm, const double* __restrict__ ratio,
+                                                               const double* __restrict__ u, float* __restrict__ batch,
+                                                               int* __restrict__ labels) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= entries) return;
+  const int i = (int)(e / npoint), j = (int)(e % npoint);
+  const long id = order[i];
+  if (id < 0 || id >= n_shapes) return;
+  if (j == 0) labels[i] = shape_labels[id];
+  const int p = perm[u[e] <= ratio[i] ? 0 : j];  // P:250-252 behind P:47-49: a dropped point is the shuffled cloud's first
+  if (p < 0 || p >= npoint) return;
+  const float* __restrict__ src = prepared + ((size_t)id * npoint + p) * CH;
+  float x[CH];
+  if (CH == 6) {  // rows of 24 bytes: three 8-byte reads
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const float2 v = reinterpret_cast<const float2*>(src)[q];
+      x[2 * q] = v.x, x[2 * q + 1] = v.y;
+    }
+  } else {  // rows of 12 bytes are 8-byte aligned at every other row only
+#pragma unroll
+    for (int q = 0; q < CH; ++q) x[q] = src[q];
+  }
+  const double s = scale[i];
+  if (mats) {
+    const double* __restrict__ a = mats + (size_t)i * 18;
+#pragma unroll
+    for (int h = 0; h < CH; h += 3) {
+      double v[3] = {(double)x[h], (double)x[h + 1], (double)x[h + 2]}, w[3];
+      ma_dot(v, a, w);
+      if (CH == 3) {  // P:59: rotate_point_cloud allocates float32
+#pragma unroll
+        for (int c = 0; c < 3; ++c) w[c] = (double)(float)w[c];
+      }
+      ma_dot(w, a + 9, v);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) x[h + c] = (float)v[c];  // P:118,188: float32
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {  // float32 *= float64, float32 += float64: each rounds
+      const float t = (float)((double)x[c] * s);
+      x[c] = (float)((double)t + shift[i * 3 + c]);
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = (float)(((double)x[c] * s) + shift[i * 3 + c]);  // float64 until the feed
+  }
+  float* __restrict__ dst = batch + (size_t)e * CH;
+  if (CH == 6) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) reinterpret_cast<float2*>(dst)[q] = make_float2(x[2 * q], x[2 * q + 1]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < CH; ++q) dst[q] = x[q];
   }
 }
 
@@ -246,6 +317,24 @@ extern "C" int pasnl_modelnet_batch(int b, int bsize, int npoint, int ch, const 
   const long per_shape = (long)npoint * ch, entries = (long)bsize * per_shape;
   hipLaunchKernelGGL(modelnet_batch_kernel, dim3(wt_blocks(entries, 256)), dim3(256), 0, pasnl_hip_stream(stream), entries, bsize, per_shape,
                      order + start, n_shapes, prepared, shape_labels, batch, labels);
+  return pasnl_launch_status();
+}
+
+extern "C" int pasnl_modelnet_augment(int b, int bsize, int npoint, int ch, const int* order, long n_order, long start, long n_shapes,
+                                      const float* prepared, const int* shape_labels, const double* mats, const double* scale,
+                                      const double* shift, const int* perm, const double* ratio, const double* u, float* batch,
+                                      int* labels, pasnl_stream_t stream) {
+  PASNL_REQUIRE(b >= 0 && bsize >= 0 && bsize <= b && npoint >= 1 && (ch == 3 || ch == 6) && n_shapes >= 0 && start >= 0 &&
+                    n_order >= 0 && start + bsize <= n_order, PASNL_EINVAL);
+  if (bsize == 0) return PASNL_OK;
+  PASNL_REQUIRE(order && prepared && shape_labels && scale && shift && perm && ratio && u && batch && labels, PASNL_ENULL);
+  const long entries = (long)bsize * npoint;
+  if (ch == 6)
+    hipLaunchKernelGGL(modelnet_augment_kernel<6>, dim3(wt_blocks(entries, 256)), dim3(256), 0, pasnl_hip_stream(stream), entries, bsize,
+                       npoint, order + start, n_shapes, prepared, shape_labels, mats, scale, shift, perm, ratio, u, batch, labels);
+  else
+    hipLaunchKernelGGL(modelnet_augment_kernel<3>, dim3(wt_blocks(entries, 256)), dim3(256), 0, pasnl_hip_stream(stream), entries, bsize,
+                       npoint, order + start, n_shapes, prepared, shape_labels, mats, scale, shift, perm, ratio, u, batch, labels);
   return pasnl_launch_status();
 }
 
