@@ -28,7 +28,9 @@ import numpy as np
 import torch
 
 from pointasnl_amd import _hip
-from pointasnl_amd.SemanticKITTI.scan_tester import ORDER_CAP, _p, project
+from pointasnl_amd.SemanticKITTI.scan_tester import ORDER_CAP, project
+
+_p = _hip.ptr
 
 DESC_BYTES = 48  # sizeof(pasnl_scene_crop_t)
 SMOOTH = {"test": 0.98, "validation": 0.95}  # T:101, 234

@@ -23,51 +23,29 @@ the reference ON THE SAME MACHINE; across machines the blocks (and everything af
 Deviations: the rows past the last real one of a scene's final batch are fed zeros (the reference leaves stale rows there
 and never votes them); split='train' is refused (its label weights can be inf or nan); no file is written -- `export`
 returns the array the reference writes line by line.  Coordinates must be finite.
+
+The host steps shared with the SemanticKITTI loop are `WindowLoop`'s (window_loop.py); in this reference they are grid
+D:214-217, count D:223-233, fill D:229-241, centers D:225-226 and 242, merged D:232-233, merge_blocks D:244-269 with
+nearest_block_literal D:176-181, draw_rows D:281-287 (a make-up longer than its block pads short, as the reference's slice
+does), blocks D:183-300, vote T:159-161, run T:122-180, score T:163-170, class_iou T:189.
 """
 import ctypes
+import functools
 import math
 
 import numpy as np
 import torch
 
-from pointasnl_amd import _hip
-from pointasnl_amd.SemanticKITTI.scan_tester import _p
+from pointasnl_amd import _hip, window_loop
+from pointasnl_amd.window_loop import WindowLoop, nearest_block_literal
 
+_p = _hip.ptr
 TEST_CLASS = np.array([0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])  # T:105
+nearest_block = nearest_block_literal  # D:176-181: a few dozen windows, the reference's own loop
+merge_blocks = functools.partial(window_loop.merge_blocks, nearest=nearest_block)  # D:244-269; centres as a list or (m,2)
 
 
-def nearest_block(center, centers):
-    """D:176-181, through numpy exactly so (see the module docstring on ties)"""
-    dist = np.zeros(len(centers))
-    for i in range(len(centers)):
-        dist[i] = np.linalg.norm(centers[i] - center, ord=2)
-    return np.argsort(dist)[0]
-
-
-def merge_blocks(sizes, centers, min_block_points=4096):
-    """D:244-269 over counts and centres: a block of at most min_block_points points is popped and appended to the nearest
-    remaining block, and the cursor does not advance.  -> per final block, the ordered positions (into `sizes`) of the
-    windows whose member lists are concatenated."""
-    sizes, centers = [int(s) for s in sizes], [np.asarray(c, np.float64) for c in centers]
-    if not sizes:
-        raise ValueError("no non-empty window")
-    parts = [[k] for k in range(len(sizes))]
-    at = 0
-    while at < len(sizes):
-        if sizes[at] > min_block_points:
-            at += 1
-            continue
-        size, center, part = sizes.pop(at), centers.pop(at), parts.pop(at)
-        if not sizes:
-            raise ValueError(f"every block holds at most min_block_points = {min_block_points} points: the reference's "
-                             "nearest_dist would run on an empty list")
-        to = nearest_block(center, centers)
-        sizes[to] += size
-        parts[to] = parts[to] + part
-    return parts
-
-
-class WindowTester:
+class WindowTester(WindowLoop):
     """`WindowTester(scenes, labels=labels, num_classes=21, block_points=8192, batch_size=6, stride=0.5, with_rgb=True,
     noise_ratio=0.2, min_block_points=4096, rng=np.random)`.
 
@@ -76,6 +54,8 @@ class WindowTester:
     moves back).  labels: the reference's semantic_labels_list, values in [0, num_classes) (None: zeros).  rng: np.random
     or a RandomState; `blocks(i)` draws rng.choice(n, ceil(noise_ratio * n)), rng.randn(that, 3), then per block
     rng.shuffle (when its length is no multiple of block_points) and rng.shuffle again."""
+    ITEM, ENTRY, SCALARS, MASKED, PAD_SHORT = "scene", "pasnl_window", ("stride",), True, True
+    block_size, scored, nearest = 1.5, True, staticmethod(nearest_block_literal)  # D:226; labelweights are ones; D:176-181
 
     def __init__(self, scenes, labels=None, num_classes=21, block_points=8192, batch_size=6, stride=0.5, with_rgb=True,
                  noise_ratio=0.2, min_block_points=4096, rng=np.random, split="test"):
@@ -134,89 +114,22 @@ class WindowTester:
                     self.serial, _p(self.stamp[i]), _p(self.stats))
         return self.serial
 
-    def grid(self, i):
-        """D:214-217: coordmin / coordmax on the device, read back (the first of a vote's two readbacks), and the number of
-        windows per axis as the reference computes it.  -> coordmin (3,) f32, coordmax (3,) f32, nx, ny."""
-        _hip.launch("pasnl_window_bounds", "WindowTester bounds", ctypes.c_long(self.sizes[i]), _p(self.xyz[i]), _p(self.bounds))
-        b = self.bounds.cpu().numpy()
-        coordmin, coordmax = b[0:3].copy(), b[3:6].copy()
-        if not np.all(np.isfinite(b)):
-            raise ValueError(f"scene {i} has no finite extent (a scene whose points coincide divides by zero in the noise step)")
-        nx = int(np.ceil((coordmax[0] - coordmin[0]) / self.stride).astype(np.int32))
-        ny = int(np.ceil((coordmax[1] - coordmin[1]) / self.stride).astype(np.int32))
-        if nx < 1 or ny < 1:
-            raise ValueError(f"scene {i} has zero extent in x or y: the reference finds no window")
-        return coordmin, coordmax, nx, ny
-
-    def count(self, i, nx, ny):
-        """D:223-233, counted: -> the scanned histogram (a device buffer pasnl_window_fill reads) and the per-window counts
-        (nx*ny,) as numpy, the second readback."""
-        n = self.sizes[i]
-        nbytes = int(_hip.lib().pasnl_window_hist_bytes(ctypes.c_long(n), nx, ny))
-        if nbytes == 0:
-            raise _hip.PasnlUnsupported(f"{nx} x {ny} windows: their positions do not fit an int32")
-        hist = torch.empty((nbytes // 4,), dtype=torch.int32, device=self.device)
-        counts = torch.empty((nx * ny,), dtype=torch.int32, device=self.device)
-        _hip.launch("pasnl_window_count", "WindowTester count", ctypes.c_long(n), _p(self.xyz[i]), _p(self.bounds), nx, ny,
-                    ctypes.c_double(self.stride), _p(hist), _p(counts))
-        return hist, counts.cpu().numpy().astype(np.int64)
-
-    def fill(self, i, nx, ny, hist, woff, cap):
-        """D:229-241: the member lists, each at woff[w] -> cat_idx (cap,) i32, cat_mask (cap,) u8 device tensors"""
-        cat_idx = torch.empty((cap,), dtype=torch.int32, device=self.device)
-        cat_mask = torch.empty((cap,), dtype=torch.uint8, device=self.device)
-        w = _hip.as_dev(np.asarray(woff, np.int32), torch.int32)
-        _hip.launch("pasnl_window_fill", "WindowTester fill", ctypes.c_long(self.sizes[i]), _p(self.xyz[i]), _p(self.bounds), nx, ny,
-                    ctypes.c_double(self.stride), _p(hist), _p(w), ctypes.c_long(cap), _p(cat_idx), _p(cat_mask))
-        return cat_idx, cat_mask
-
-    def centers(self, coordmin, coordmax, nx, ny, windows):
-        """D:225-226, 242 for the listed windows -> (len, 2) float64 block centres"""
-        out = []
-        for w in windows:
-            i, j = divmod(int(w), ny)
-            curmin = coordmin + [i * self.stride, j * self.stride, 0]
-            curmax = curmin + [1.5, 1.5, coordmax[2] - coordmin[2]]
-            out.append((curmin[0:2] + curmax[0:2]) / 2.0)
-        return out
+    def merged(self, counts):
+        return np.flatnonzero(counts > 0)  # D:232-233: empty windows are skipped
 
     def prepare(self, i):
-        """Steps 1-4 up to the gather: move, windows, merge, the rows' positions.  -> dict(rows, rowpos, cat_idx, cat_mask,
-        cap, serial, blocks) where `blocks` lists per final block its windows in concatenation order."""
+        """Steps 1-4 up to the gather: the move, then WindowLoop.prepare with the step's `serial` added."""
         serial = self.move(i)
-        coordmin, coordmax, nx, ny = self.grid(i)
-        hist, counts = self.count(i, nx, ny)
-        found = np.flatnonzero(counts > 0)  # D:232-233: empty windows are skipped
-        parts = merge_blocks(counts[found], self.centers(coordmin, coordmax, nx, ny, found), self.min_block_points)
-        cap = int(counts.sum())
-        if cap >= 2 ** 31:
-            raise _hip.PasnlUnsupported("the windows hold 2^31 or more members")
-        woff = np.full(nx * ny, -1, np.int64)
-        at, rowpos = 0, []
-        for part in parts:
-            start = at
-            for k in part:
-                woff[found[k]] = at
-                at += int(counts[found[k]])
-            order = np.arange(at - start)  # D:281-287
-            if order.shape[0] % self.P != 0:
-                makeup = self.P - order.shape[0] % self.P
-                self.rng.shuffle(order)
-                order = np.concatenate((order, order[0:makeup].copy()))
-            self.rng.shuffle(order)
-            rowpos.append((order + start).astype(np.int32))
-        rowpos = np.concatenate(rowpos)
-        cat_idx, cat_mask = self.fill(i, nx, ny, hist, woff, cap)
-        return dict(rows=rowpos.shape[0] // self.P, rowpos=torch.from_numpy(rowpos).to(self.device), cat_idx=cat_idx, cat_mask=cat_mask,
-                    cap=cap, serial=serial, blocks=[[int(found[k]) for k in part] for part in parts])
+        return dict(WindowLoop.prepare(self, i), serial=serial)
+
+    def _buffers(self, rows):
+        return (torch.empty((rows, self.P, self.width), dtype=torch.float32, device=self.device),) + tuple(
+            torch.empty((rows, self.P), dtype=torch.int32, device=self.device) for _ in range(3))
 
     def gather(self, i, prep, start, rows, out=None):
         """D:289-300 for rows [start, start + rows) of the prepared vote; rows past the last one come out as zeros.
         -> data (rows,P,3|6) f32, labels, weights (0/1), indices (rows,P) i32, device tensors."""
-        if out is None:
-            out = (torch.empty((rows, self.P, self.width), dtype=torch.float32, device=self.device),) + tuple(
-                torch.empty((rows, self.P), dtype=torch.int32, device=self.device) for _ in range(3))
-        data, lab, wgt, idx = out
+        data, lab, wgt, idx = self._buffers(rows) if out is None else out
         real = max(0, min(rows, prep["rows"] - start))
         _hip.launch("pasnl_window_gather", "WindowTester gather", rows, real, self.P, _p(prep["rowpos"], start * self.P * 4),
                     ctypes.c_long(prep["cap"]), _p(prep["cat_idx"]), _p(prep["cat_mask"]), ctypes.c_long(self.sizes[i]), _p(self.xyz[i]),
@@ -224,78 +137,19 @@ class WindowTester:
                     _p(self.stamp[i]), prep["serial"], _p(data), _p(lab), _p(wgt), _p(idx))
         return data, lab, wgt, idx
 
-    def blocks(self, i):
-        """One `__getitem__(i)` of the reference on the device: moves the scene, advances the RNG.  -> device tensors data
-        (R,P,3|6) f32, labels (R,P) i32, weights (R,P) i32 (1 where the reference's float64 weight is 1.0), indices (R,P) i32."""
-        prep = self.prepare(i)
-        return self.gather(i, prep, 0, prep["rows"])
+    def _batch(self, i, prep, start, out):
+        data, _, wgt, idx = self.gather(i, prep, start, self.B, out)
+        return data, idx, wgt
 
-    def window_lists(self, i):
-        """The windows of scene i as it stands (no move, no RNG draw), every non-empty window's list in window order
-        -> coordmin, coordmax, (nx, ny), counts (nx*ny,) int64, members i32, masks u8 (numpy; the lists back to back)."""
-        coordmin, coordmax, nx, ny = self.grid(i)
-        hist, counts = self.count(i, nx, ny)
-        woff = np.where(counts > 0, np.cumsum(counts) - counts, -1)
-        cap = max(int(counts.sum()), 1)
-        cat_idx, cat_mask = self.fill(i, nx, ny, hist, woff, cap)
-        total = int(counts.sum())
-        return coordmin, coordmax, (nx, ny), counts, cat_idx[:total].cpu().numpy(), cat_mask[:total].cpu().numpy()
-
-    # ---- the loop
-    def vote(self, i, logits, idx, wgt, rows):
-        """T:159-161 for the first `rows` rows of a batch: logits (B,P,C) f32"""
-        v = _hip.as_dev(logits, torch.float32)
-        if v.numel() < rows * self.P * self.C or v.shape[-1] != self.C:
-            raise ValueError(f"the forward must return (B, {self.P}, {self.C}) logits")
-        _hip.launch("pasnl_window_vote", "WindowTester vote", rows, self.P, self.C, _p(v), _p(idx), _p(wgt), ctypes.c_long(self.sizes[i]),
-                    _p(self.pools[i]))
-
-    def run(self, forward, num_votes=1):
-        """T:122-180: scenes in order, num_votes votes of each inside (the reference's RNG order).  forward: (B,P,3|6) f32
-        device tensor -> (B,P,C) f32 logits.  Within a vote, gather -> forward -> vote runs batch after batch with no host
-        synchronisation.  -> the number of rows fed."""
-        fed = 0
-        out = (torch.empty((self.B, self.P, self.width), dtype=torch.float32, device=self.device),) + tuple(
-            torch.empty((self.B, self.P), dtype=torch.int32, device=self.device) for _ in range(3))
-        for i in range(self.S):
-            self.pools[i] = torch.zeros((self.sizes[i], self.C), dtype=torch.int32, device=self.device)
-            for _ in range(num_votes):
-                prep = self.prepare(i)
-                for start in range(0, prep["rows"], self.B):
-                    data, _, wgt, idx = self.gather(i, prep, start, self.B, out)
-                    self.vote(i, forward(data), idx, wgt, min(self.B, prep["rows"] - start))
-                fed += prep["rows"]
-            self.score(i)
-        return fed
-
-    def score(self, i):
-        """T:163-170 for scene i: pred_label on the device, then seen / correct / iou_deno from the confusion matrix of
-        (labels, pred_label), added to the totals."""
-        n = self.sizes[i]
-        pred = torch.empty((n,), dtype=torch.int32, device=self.device)
-        _hip.launch("pasnl_window_pool_labels", "WindowTester labels", ctypes.c_long(n), self.C, _p(self.pools[i]), _p(pred))
-        cm = torch.zeros((self.C, self.C), dtype=torch.int64, device=self.device)
-        _hip.launch("pasnl_confusion_matrix", "WindowTester counts", ctypes.c_long(n), _p(self.labels[i]), _p(pred), _p(self.class_values),
-                    self.C, _p(cm))
-        m = cm.cpu().numpy()  # rows: the truth
-        seen, correct = m.sum(axis=1), np.diagonal(m).copy()
-        labelled = m[1:].sum(axis=0)                      # predictions of l among the points with label > 0
-        deno = labelled + np.where(np.arange(self.C) > 0, seen - correct, 0)  # ((pred == l) | (label == l)) & (label > 0)
-        self.preds[i], self.counts[i] = pred, np.stack([seen, correct, deno])
-        self.total += self.counts[i]
+    def deno(self, m, seen, correct):
+        """T:170: ((pred == l) | (label == l)) & (label > 0)"""
+        labelled = m[1:].sum(axis=0)  # predictions of l among the points with label > 0
+        return labelled + np.where(np.arange(self.C) > 0, seen - correct, 0)
 
     # ---- state and results
     def points(self, i):
         """scene i's xyz as moved so far, (n_i, 3) f32 device tensor"""
         return self.xyz[i]
-
-    def pool(self, i):
-        """scene i's vote counters (n_i, C) i32, device tensor"""
-        return self.pools[i]
-
-    def pred_label(self, i):
-        """np.argmax(vote_label_pool, 1) of scene i, (n_i,) i32 device tensor"""
-        return self.preds[i]
 
     def scene_counts(self, i):
         """-> seen, correct, iou_deno of scene i, (C,) int64 each (T:168-170)"""
@@ -306,15 +160,6 @@ class WindowTester:
         seen, correct, deno = self.scene_counts(i)
         iou_map = np.array(correct) / (np.array(deno, dtype=float) + 1e-6)
         return iou_map, np.mean(iou_map[np.array(seen) != 0])
-
-    def totals(self):
-        """-> total_seen_class, total_correct_class, total_iou_deno_class over the scenes scored so far (T:165-167)"""
-        return tuple(self.total.copy())
-
-    def class_iou(self):
-        """T:189: the IoU of classes 1..C-1 over all scenes; its mean is the reference's 'point avg class IoU'"""
-        _, correct, deno = self.totals()
-        return np.array(correct[1:]) / (np.array(deno[1:], dtype=float) + 1e-6)
 
     def export(self, i, scene_points_id, scene_points_num, test_class=TEST_CLASS):
         """T:179-180: whole = zeros(scene_points_num); whole[scene_points_id] = test_class[pred_label] -> (num,) f64 numpy,

@@ -45,8 +45,8 @@ import torch
 
 from pointasnl_amd import _hip
 from pointasnl_amd.block_loop import BlockLoop
-from pointasnl_amd.SemanticKITTI.scan_tester import _p
 
+_p = _hip.ptr
 TRIES = 10  # D:81
 
 

@@ -26,8 +26,7 @@ DESC_BYTES = 40     # sizeof(pasnl_scan_crop_t)
 ORDER_CAP = 14336   # pasnl_crop_order_permute: kcap limit of the LDS sort
 
 
-def _p(t, byte_offset=0):
-    return ctypes.c_void_p(_hip.ptr(t).value + byte_offset)
+_p = _hip.ptr
 
 
 class ScanTester:

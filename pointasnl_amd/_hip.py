@@ -84,15 +84,15 @@ def stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def ptr(t):
-    """Device pointer of a tensor for a launch on torch's CURRENT stream: the tensor has to live on the current device
-    (launching on cuda:0's stream with cuda:1's memory would fault or silently use the wrong GPU)."""
+def ptr(t, byte_offset=0):
+    """Device pointer of a tensor, byte_offset bytes in, for a launch on torch's CURRENT stream: the tensor has to live on the
+    current device (launching on cuda:0's stream with cuda:1's memory would fault or silently use the wrong GPU)."""
     if t is None:
         return ctypes.c_void_p(0)
     if t.device.index != torch.cuda.current_device():
         raise PasnlError(f"tensor on {t.device} but the current device is cuda:{torch.cuda.current_device()}: wrap the call in "
                          "`with torch.cuda.device(tensor.device):` (launches go to the current device's stream)")
-    return ctypes.c_void_p(t.data_ptr())
+    return ctypes.c_void_p(t.data_ptr() + byte_offset)
 
 
 # Optional per-launch timing for bench.py: when PROFILE is a list, every C-ABI launch is bracketed by two

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from pointasnl_amd import _hip
-from pointasnl_amd.SemanticKITTI.scan_tester import _p
+
+_p = _hip.ptr
 
 
 class BlockLoop:

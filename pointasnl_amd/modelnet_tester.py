@@ -36,8 +36,7 @@ from pointasnl_amd import _hip
 NOISE_POINT = (1, 10, 50, 100)  # T:34
 
 
-def _p(t, byte_offset=0):
-    return ctypes.c_void_p(_hip.ptr(t).value + byte_offset)
+_p = _hip.ptr
 
 
 def fps_cap():

@@ -38,7 +38,9 @@ import numpy as np
 import torch
 
 from pointasnl_amd import _hip
-from pointasnl_amd.modelnet_tester import ModelNetTester, _p
+from pointasnl_amd.modelnet_tester import ModelNetTester
+
+_p = _hip.ptr
 
 
 def rotation_about_y(u):
