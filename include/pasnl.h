@@ -541,7 +541,8 @@ int pasnl_grid_subsample(long n, int fdim, int ldim, const float* points, const 
  * for every crop) nearest, clamped to [0, min(n, kcap)].
  * -> out_idx (b,kcap) i32: the selected indices in ASCENDING INDEX order (crop_pc shuffles them at once, :274; sort by
  * out_d2 for KDTree.query's order), entries behind the count are not written; out_d2 (b,kcap) f64 their squared
- * distances (NULL: not wanted), entries behind the count not written either; out_count (b) i32: the number selected (radius form: the TRUE number within the radius,
+ * distances (NULL: not wanted), entries behind the count not written either (a point with a NaN coordinate has d2 = NaN
+ * and ranks behind +inf, lowest index first; its out_d2 is that NaN with the sign bit clear); out_count (b) i32: the number selected (radius form: the TRUE number within the radius,
  * which may exceed kcap -- only the first kcap by index are stored).
  * An exact radix selection on the 63 key bits (no tree), 8 launches, no host synchronisation.
  * workspace: pasnl_knn_crop_workspace_bytes(b, n) bytes (8 n per crop for the keys + histograms). */

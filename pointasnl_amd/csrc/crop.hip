@@ -31,7 +31,7 @@ constexpr int CR_ITEMS = 8;                       // consecutive points per thre
 constexpr int CR_BLOCK = CR_THREADS * CR_ITEMS;   // points per workgroup
 constexpr int CR_BITS = 13;
 constexpr int CR_BINS = 1 << CR_BITS;
-constexpr int CR_PASSES = 5;                      // 13 + 13 + 13 + 13 + 11 = 63 bits (bit 63, the sign, is always clear)
+constexpr int CR_PASSES = 5;                      // 13 + 13 + 13 + 13 + 11 = 63 bits (bit 63, the sign: cr_key clears it)
 __host__ __device__ constexpr int cr_shift(int p) { return p == 0 ? 50 : (p == 1 ? 37 : (p == 2 ? 24 : (p == 3 ? 11 : 0))); }
 __host__ __device__ constexpr int cr_width(int p) { return p == 4 ? 11 : 13; }
 
@@ -63,7 +63,9 @@ __device__ __forceinline__ unsigned long long cr_key(const float* __restrict__ p
   // sklearn's EuclideanDistance.rdist on float64 copies of the float32 coordinates: d = 0; d += t*t per axis, in order
   const double dx = (double)p[0] - cx, dy = (double)p[1] - cy, dz = (double)p[2] - cz;
   const double d2 = (dx * dx + dy * dy) + dz * dz;  // (-ffp-contract=off: no fused operations)
-  return (unsigned long long)__double_as_longlong(d2);
+  // d2 is never negative, but a NaN coordinate's sign bit survives the arithmetic: cleared here, every key has bit 63 clear
+  // (what the passes and the start state rely on) and such a point ranks and is returned as the positive NaN
+  return (unsigned long long)__double_as_longlong(d2) & 0x7FFFFFFFFFFFFFFFull;
 }
 
 // D (pasnl_knn_crop_indirect, pasnl_knn_crop_scene): crop c reads its scan's offset, point count, centre and k from desc[c]
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(ST_THREADS) void scene_pick_init_kernel(int s, cons
 }
 
 // The boundary bin of histogram `h` for the r-th key (r >= 1, r <= total): every thread returns the same (bin, keys before it,
-// keys in it).  sh: CR_THREADS / 64 + 3 ints of LDS.
+// keys in it).  An r past the total matches no bin: (0, 0, 0) then, not LDS nobody wrote.  sh: CR_THREADS / 64 + 3 ints of LDS.
 __device__ __forceinline__ void cr_find_bin(const unsigned* __restrict__ h, int r, int* sh, int& bin, int& before, int& inbin) {
   constexpr int PER = CR_BINS / CR_THREADS;  // 32 consecutive bins per thread
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -154,6 +156,7 @@ __device__ __forceinline__ void cr_find_bin(const unsigned* __restrict__ h, int 
   }
   const int incl = wave_inclusive_sum_i32(sum);
   if (lane == 63) sh[wave] = incl;
+  if (tid < 3) sh[CR_THREADS / 64 + tid] = 0;
   __syncthreads();
   int base = incl - sum;
   for (int w = 0; w < wave; ++w) base += sh[w];
