@@ -951,6 +951,32 @@ size_t pasnl_block_score_workspace_bytes(void);
 int pasnl_block_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw, long long* counters,
                       double* loss, void* workspace, pasnl_stream_t stream);
 
+/* The transform of the training input loop (T:253-254 of `train_one_epoch`, T:233-276), the other order: rotate_point_cloud_z
+ * (P:71-89) first, then normalize_data (P:8-24), for rows blocks of src (rows,block_points,width) f32 into batch, one
+ * workgroup per block, one launch.  The float32 row is widened to float64; x' = x * cos + y * (-sin), y' = x * sin + y * cos
+ * with rot (rows,2) f64 = the host's cos and sin of each row's angle (required: NULL is PASNL_ENULL), the explicit sums of
+ * pasnl_block_normalize (within one float32 ulp of numpy's product, whose dgemm fixes no summation order); z is carried --
+ * x*0 + y*0 + z*1 is z for finite input up to the sign of a zero, and the centroid subtraction below removes that sign unless
+ * the centroid is exactly zero.  The three coordinates are ROUNDED TO FLOAT32, as `rotated_data` is float32; on that float32
+ * block normalize_data runs as in pasnl_block_normalize: the centroid's float64 chains / float64(block_points), pc - centroid,
+ * m = max(sqrt((x*x + y*y) + z*z)), pc / m, rounded to float32.  The two orders do not give the same bits.  A block whose
+ * rows are all one point has m == 0 and gets the reference's NaN (0 / 0).  Columns 3.. are copied.  The rounded block is held
+ * in batch between the two stages, and every row of src is read before that row of batch is written: src == batch is
+ * allowed; any other overlap is not. */
+int pasnl_block_train_batch(int rows, int block_points, int width, const float* src, const double* rot, float* batch,
+                            pasnl_stream_t stream);
+
+/* The tallies of one training batch (T:264-272): pred = np.argmax(logits, 2) as in pasnl_block_score (the FIRST maximum,
+ * numpy's NaN rule); counters (3) i64 += total_correct = np.sum(pred == label), total_seen = rows * block_points and
+ * total_iou_deno = sum over l of np.sum((pred == l) | (label == l)) -- 1 for an entry whose prediction and label agree, 2
+ * for one where they differ -- over EVERY entry, with no smpw > 0 and no label > 0: integers, exact and order-free.  Labels
+ * are in [0, c) by the callers' checks; an entry outside that range is skipped (it counts nowhere, total_seen included), as
+ * in pasnl_block_score.  loss[1] = the batch's classify loss and loss[0] += loss[1], defined and computed as there (the same
+ * code: sum(w * ce) / count(w != 0), 0 when that count is 0; a tolerance, never bits).  workspace:
+ * pasnl_block_score_workspace_bytes() device bytes.  c <= 256, else PASNL_EUNSUPPORTED.  Two launches. */
+int pasnl_block_train_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw,
+                            long long* counters, double* loss, void* workspace, pasnl_stream_t stream);
+
 /* ---- SemanticKITTI's training-time validation loops on the device (SemanticKITTI/semantic_kitti_dataset.py (D) :68-109
  * `SemanticKittiDataset.__getitem__` and :164-211 `SemanticKittiDataset_whole.__getitem__`; SemanticKITTI/train_semantic_kitti.py
  * (T) :267-328 `eval_one_epoch` and :331-418 `eval_whole_scene_one_epoch`; utils/provider.py (P) :71-89

@@ -78,6 +78,15 @@ class ScannetDataset(_BlockDataset):
     def __getitem__(self, index):
         return self._host(*self.tester.item(index))
 
+    @property
+    def trainer(self):
+        """`train_one_epoch` of train_scannet.py on the device, over the same tester (block_trainer.py); built on first use"""
+        if getattr(self, "_trainer", None) is None:
+            from pointasnl_amd.ScanNet.block_trainer import BlockTrainer
+
+            self._trainer = BlockTrainer(tester=self.tester)
+        return self._trainer
+
 
 class ScannetDatasetWholeScene(_BlockDataset):
     """`ScannetDatasetWholeScene(root, block_points=8192, split='val', with_rgb=False)` (:69-90); `ds[i]` is :92-129:

@@ -72,6 +72,16 @@ class SemanticKittiDataset(_BlockDataset):
     def __getitem__(self, index):
         return tuple(a.cpu().numpy() for a in self.tester.item(index))
 
+    @property
+    def trainer(self):
+        """`train_one_epoch` of train_semantic_kitti.py on the device, over the same tester (block_trainer.py); built on
+        first use"""
+        if getattr(self, "_trainer", None) is None:
+            from pointasnl_amd.SemanticKITTI.block_trainer import KittiBlockTrainer
+
+            self._trainer = KittiBlockTrainer(tester=self.tester)
+        return self._trainer
+
 
 class SemanticKittiDataset_whole(_BlockDataset):
     """`SemanticKittiDataset_whole(...)` with the same arguments; `ds[i]` is :164-211: (R, sample_points, 3|4) f32,

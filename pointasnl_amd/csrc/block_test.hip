@@ -13,6 +13,9 @@
 //   chopped: per try pasnl_block_crop_stats -> [four integers down]; then [choices up] -> pasnl_block_fill -> pasnl_block_gather
 //   whole:   pasnl_block_grid_count -> [nx*ny counts down; choices up] -> pasnl_block_fill -> pasnl_block_gather
 //   per batch, with no synchronisation: pasnl_block_normalize -> forward -> pasnl_block_score
+// The training input loop (T:233-276 `train_one_epoch`, and SemanticKITTI/train_semantic_kitti.py:223-264) draws the same
+// chopped items in a shuffled order; per batch: pasnl_block_train_batch (rotate, round, normalize: the other order; the
+// SemanticKITTI loop only rotates, pasnl_kblock_rotate) -> step -> pasnl_block_train_score (tallies over every entry).
 #include <math.h>
 #include "common.hpp"
 #include "test_loop.hpp"
@@ -123,13 +126,10 @@ __global__ __launch_bounds__(256) void block_gather_kernel(long entries, const i
 // ---- P:8-24 (+ P:71-89): one block of the batch per workgroup, in float64 as both loops hold the batch
 constexpr int BN_TILE = 2048;  // rows per staged tile: 48 KiB of LDS
 
-__global__ __launch_bounds__(ST_THREADS) void block_normalize_kernel(int npoint, int width, const float* __restrict__ src,
-                                                                     const double* __restrict__ rot, float* __restrict__ batch) {
-  __shared__ double tile[BN_TILE * 3];
-  __shared__ double cen[3], shm[ST_WAVES];
+// P:19-21 of one block p (npoint,width) f32 by its workgroup: cen[] = per column the float64 chain / float64(npoint); -> m =
+// max sqrt((x*x + y*y) + z*z) of the centred rows, in every thread.  It only reads p (its stores go to LDS).
+__device__ __forceinline__ double block_centre_radius(int npoint, int width, const float* p, double* tile, double* cen, double* shm) {
   const int tid = threadIdx.x;
-  const float* __restrict__ p = src + (size_t)blockIdx.x * npoint * width;
-  float* __restrict__ out = batch + (size_t)blockIdx.x * npoint * width;
   double acc = -0.0;
   for (int base = 0; base < npoint; base += BN_TILE) {
     const int cnt = npoint - base < BN_TILE ? npoint - base : BN_TILE;
@@ -152,6 +152,17 @@ __global__ __launch_bounds__(ST_THREADS) void block_normalize_kernel(int npoint,
   m = shm[0];
 #pragma unroll
   for (int w = 1; w < ST_WAVES; ++w) m = nan_max(m, shm[w]);
+  return m;
+}
+
+__global__ __launch_bounds__(ST_THREADS) void block_normalize_kernel(int npoint, int width, const float* __restrict__ src,
+                                                                     const double* __restrict__ rot, float* __restrict__ batch) {
+  __shared__ double tile[BN_TILE * 3];
+  __shared__ double cen[3], shm[ST_WAVES];
+  const int tid = threadIdx.x;
+  const float* __restrict__ p = src + (size_t)blockIdx.x * npoint * width;
+  float* __restrict__ out = batch + (size_t)blockIdx.x * npoint * width;
+  const double m = block_centre_radius(npoint, width, p, tile, cen, shm);
   const bool turn = rot != nullptr;
   const double cosval = turn ? rot[blockIdx.x * 2] : 1.0, sinval = turn ? rot[blockIdx.x * 2 + 1] : 0.0;
   for (int i = tid; i < npoint; i += ST_THREADS) {
@@ -170,6 +181,81 @@ __global__ __launch_bounds__(ST_THREADS) void block_normalize_kernel(int npoint,
   }
 }
 
+// ---- T:253-254, the training order: rotate_point_cloud_z (P:71-89) on the float64 batch, its result ROUNDED TO FLOAT32
+// (rotated_data is float32), then normalize_data (P:8-24) on that float32 block widened again.  One block per workgroup, one
+// launch.  The rounded block is held in the output: a thread reads its own rows of src before it writes them (src == batch is
+// allowed), and behind the barrier the workgroup reads back what it wrote.  z is carried: x*0 + y*0 + z*1 is z for finite
+// input up to the sign of a zero, which the centroid subtraction removes unless the centroid is exactly zero.
+__global__ __launch_bounds__(ST_THREADS) void block_train_batch_kernel(int npoint, int width, const float* src, const double* __restrict__ rot,
+                                                                       float* batch) {
+  __shared__ double tile[BN_TILE * 3];
+  __shared__ double cen[3], shm[ST_WAVES];
+  const int tid = threadIdx.x;
+  const float* p = src + (size_t)blockIdx.x * npoint * width;
+  float* out = batch + (size_t)blockIdx.x * npoint * width;
+  const double cosval = rot[blockIdx.x * 2], sinval = rot[blockIdx.x * 2 + 1];
+  for (int i = tid; i < npoint; i += ST_THREADS) {
+    const float* r = p + (size_t)i * width;
+    float* o = out + (size_t)i * width;
+    const double x = (double)r[0], y = (double)r[1];
+    const float ox = (float)(x * cosval + y * -sinval), oy = (float)(x * sinval + y * cosval);
+    for (int f = width - 1; f >= 2; --f) o[f] = r[f];
+    o[0] = ox;
+    o[1] = oy;
+  }
+  __syncthreads();
+  const double m = block_centre_radius(npoint, width, out, tile, cen, shm);  // (its last barrier is behind every read of out)
+  for (int i = tid; i < npoint; i += ST_THREADS) {
+    float* o = out + (size_t)i * width;
+    const double x = ((double)o[0] - cen[0]) / m, y = ((double)o[1] - cen[1]) / m, z = ((double)o[2] - cen[2]) / m;
+    o[0] = (float)x;
+    o[1] = (float)y;
+    o[2] = (float)z;
+  }
+}
+
+// ---- what the validation score and the training score share: the prediction, one entry's cross-entropy, the partial sums
+// np.argmax(pred_val, 2) of one row of c logits: the first maximum, the first NaN
+__device__ __forceinline__ int score_argmax(const float* row, int c) {
+  int a = 0;
+  float best = row[0];
+  bool nan = best != best;
+  for (int q = 1; q < c && !nan; ++q) {
+    const float v = row[q];
+    if (v > best || v != v) { best = v; a = q; nan = v != v; }
+  }
+  return a;
+}
+
+// the cross-entropy of one row against label l: a float32 log-sum-exp
+__device__ __forceinline__ float score_cross_entropy(const float* row, int c, int l) {
+  float mx = row[0];
+  for (int q = 1; q < c; ++q) mx = row[q] > mx ? row[q] : mx;
+  float s = 0.0f;
+  for (int q = 0; q < c; ++q) s += expf(row[q] - mx);
+  return (logf(s) + mx) - row[l];
+}
+
+// A workgroup of 256: its threads' sums of w * ce and counts of w != 0 reduced over the lanes by shuffles into shs / shn [wave];
+// its barrier is also behind every thread's LDS counting
+__device__ __forceinline__ void score_reduce(double sum, int nz, double* shs, int* shn) {
+  const int tid = threadIdx.x;
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, 64);
+    nz += __shfl_xor(nz, o, 64);
+  }
+  if ((tid & 63) == 0) { shs[tid >> 6] = sum; shn[tid >> 6] = nz; }
+  __syncthreads();
+}
+
+// ... and the four waves in order into part_sum / part_cnt [blockIdx.x]
+__device__ __forceinline__ void score_store(const double* shs, const int* shn, double* __restrict__ part_sum, long long* __restrict__ part_cnt) {
+  if (threadIdx.x == 0) {
+    part_sum[blockIdx.x] = ((shs[0] + shs[1]) + shs[2]) + shs[3];
+    part_cnt[blockIdx.x] = ((shn[0] + shn[1]) + shn[2]) + shn[3];
+  }
+}
+
 // ---- T:311-321, T:391-402: the counters (integers: exact and order-free) and the batch's weighted cross-entropy
 // counters (2 + 4c) i64: total_correct, total_seen, then seen[c], correct[c], iou_deno[c], label histogram[c]
 __global__ __launch_bounds__(256) void block_score_kernel(long entries, int c, const float* __restrict__ logits, const int* __restrict__ labels,
@@ -185,13 +271,7 @@ __global__ __launch_bounds__(256) void block_score_kernel(long entries, int c, c
   int nz = 0;
   for (long e = (long)blockIdx.x * 256 + tid; e < entries; e += (long)gridDim.x * 256) {
     const float* row = logits + (size_t)e * c;
-    int a = 0;
-    float best = row[0];
-    bool nan = best != best;
-    for (int q = 1; q < c && !nan; ++q) {  // np.argmax(pred_val, 2): the first maximum, the first NaN
-      const float v = row[q];
-      if (v > best || v != v) { best = v; a = q; nan = v != v; }
-    }
+    const int a = score_argmax(row, c);
     const int l = labels[e];
     const float w = smpw[e];
     if (l < 0 || l >= c) continue;
@@ -208,25 +288,58 @@ __global__ __launch_bounds__(256) void block_score_kernel(long entries, int c, c
       if (l > 0) atomicAdd(&cnt[1], 1);
     }
     if (w != 0.0f) {  // tf.losses.sparse_softmax_cross_entropy(weights=smpw): sum(w * ce) / count(w != 0)
-      float mx = row[0];
-      for (int q = 1; q < c; ++q) mx = row[q] > mx ? row[q] : mx;
-      float s = 0.0f;
-      for (int q = 0; q < c; ++q) s += expf(row[q] - mx);
-      sum += (double)w * (double)((logf(s) + mx) - row[l]);
+      sum += (double)w * (double)score_cross_entropy(row, c, l);
+      nz += 1;
+    }
+  }
+  score_reduce(sum, nz, shs, shn);
+  for (int k = tid; k < ncnt; k += 256)
+    if (cnt[k]) atomicAdd((unsigned long long*)&counters[k], (unsigned long long)cnt[k]);
+  score_store(shs, shn, part_sum, part_cnt);
+}
+
+// ---- T:264-272: the training tallies -- every entry counts, with no smpw > 0 and no label > 0 -- and the same loss
+// counters (3) i64: total_correct, total_seen, total_iou_deno; sum_l ((pred == l) | (label == l)) is 1 for an entry whose
+// prediction and label agree and 2 for one where they do not
+__global__ __launch_bounds__(256) void block_train_score_kernel(long entries, int c, const float* __restrict__ logits,
+                                                                const int* __restrict__ labels, const float* __restrict__ smpw,
+                                                                long long* __restrict__ counters, double* __restrict__ part_sum,
+                                                                long long* __restrict__ part_cnt) {
+  __shared__ int cnt[2];
+  __shared__ double shs[4];
+  __shared__ int shn[4];
+  const int tid = threadIdx.x;
+  if (tid < 2) cnt[tid] = 0;
+  __syncthreads();
+  double sum = 0.0;
+  int nz = 0, correct = 0, seen = 0;
+  for (long e = (long)blockIdx.x * 256 + tid; e < entries; e += (long)gridDim.x * 256) {
+    const float* row = logits + (size_t)e * c;
+    const int a = score_argmax(row, c);
+    const int l = labels[e];
+    const float w = smpw[e];
+    if (l < 0 || l >= c) continue;
+    seen += 1;
+    correct += a == l;
+    if (w != 0.0f) {
+      sum += (double)w * (double)score_cross_entropy(row, c, l);
       nz += 1;
     }
   }
   for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o, 64);
-    nz += __shfl_xor(nz, o, 64);
+    correct += __shfl_xor(correct, o, 64);
+    seen += __shfl_xor(seen, o, 64);
   }
-  if ((tid & 63) == 0) { shs[tid >> 6] = sum; shn[tid >> 6] = nz; }
-  __syncthreads();
-  for (int k = tid; k < ncnt; k += 256)
-    if (cnt[k]) atomicAdd((unsigned long long*)&counters[k], (unsigned long long)cnt[k]);
-  if (tid == 0) {
-    part_sum[blockIdx.x] = ((shs[0] + shs[1]) + shs[2]) + shs[3];
-    part_cnt[blockIdx.x] = ((shn[0] + shn[1]) + shn[2]) + shn[3];
+  if ((tid & 63) == 0) {
+    atomicAdd(&cnt[0], correct);
+    atomicAdd(&cnt[1], seen);
+  }
+  score_reduce(sum, nz, shs, shn);
+  score_store(shs, shn, part_sum, part_cnt);
+  if (tid == 0 && cnt[1]) {
+    atomicAdd((unsigned long long*)&counters[0], (unsigned long long)cnt[0]);
+    atomicAdd((unsigned long long*)&counters[1], (unsigned long long)cnt[1]);
+    atomicAdd((unsigned long long*)&counters[2], (unsigned long long)(2 * cnt[1] - cnt[0]));
   }
 }
 
@@ -305,10 +418,21 @@ extern "C" int pasnl_block_normalize(int rows, int block_points, int width, cons
   return pasnl_launch_status();
 }
 
+extern "C" int pasnl_block_train_batch(int rows, int block_points, int width, const float* src, const double* rot, float* batch,
+                                       pasnl_stream_t stream) {
+  PASNL_REQUIRE(rows >= 0 && block_points > 0 && width >= 3, PASNL_EINVAL);
+  if (rows == 0) return PASNL_OK;
+  PASNL_REQUIRE(src && rot && batch, PASNL_ENULL);
+  hipLaunchKernelGGL(block_train_batch_kernel, dim3(rows), dim3(ST_THREADS), 0, pasnl_hip_stream(stream), block_points, width, src, rot, batch);
+  return pasnl_launch_status();
+}
+
 extern "C" size_t pasnl_block_score_workspace_bytes(void) { return (size_t)BT_SCORE_GROUPS * (sizeof(double) + sizeof(long long)); }
 
-extern "C" int pasnl_block_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw,
-                                 long long* counters, double* loss, void* workspace, pasnl_stream_t stream) {
+// the validation score and the training score: one counting kernel over the entries, then the partial sums in order
+template <typename Kernel>
+static int score_launch(Kernel kernel, int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw,
+                        long long* counters, double* loss, void* workspace, pasnl_stream_t stream) {
   PASNL_REQUIRE(rows >= 0 && block_points > 0 && c >= 1, PASNL_EINVAL);
   PASNL_REQUIRE(c <= BT_CLASS_MAX, PASNL_EUNSUPPORTED);
   if (rows == 0) return PASNL_OK;
@@ -318,7 +442,17 @@ extern "C" int pasnl_block_score(int rows, int block_points, int c, const float*
   const int groups = wt_blocks(entries, 256) < (unsigned)BT_SCORE_GROUPS ? (int)wt_blocks(entries, 256) : BT_SCORE_GROUPS;
   double* part_sum = static_cast<double*>(workspace);
   long long* part_cnt = reinterpret_cast<long long*>(part_sum + BT_SCORE_GROUPS);
-  hipLaunchKernelGGL(block_score_kernel, dim3(groups), dim3(256), 0, s, entries, c, logits, labels, smpw, counters, part_sum, part_cnt);
+  hipLaunchKernelGGL(kernel, dim3(groups), dim3(256), 0, s, entries, c, logits, labels, smpw, counters, part_sum, part_cnt);
   hipLaunchKernelGGL(block_loss_kernel, dim3(1), dim3(64), 0, s, groups, part_sum, part_cnt, loss);
   return pasnl_launch_status();
+}
+
+extern "C" int pasnl_block_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw,
+                                 long long* counters, double* loss, void* workspace, pasnl_stream_t stream) {
+  return score_launch(block_score_kernel, rows, block_points, c, logits, labels, smpw, counters, loss, workspace, stream);
+}
+
+extern "C" int pasnl_block_train_score(int rows, int block_points, int c, const float* logits, const int* labels, const float* smpw,
+                                       long long* counters, double* loss, void* workspace, pasnl_stream_t stream) {
+  return score_launch(block_train_score_kernel, rows, block_points, c, logits, labels, smpw, counters, loss, workspace, stream);
 }
