@@ -360,6 +360,22 @@ int pasnl_mlp3_max_pool(int b, int n, int k0, int c1, int c2, int c3, const floa
                         const float* w1, const float* b1, const float* w2, const float* b2, float* out, long out_stride,
                         void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
 
+/* The classifier's layer 1 tail and its layer3_1 group-all module in ONE launch (csrc/mlp_pool.hip; + the pooling pass over
+ * tile maxima): pasnl_sa_tail_packed(b * n rows, ..., new_xyz, out_cat, out) followed by pasnl_mlp3_max_pool(b, n, c + 4,
+ * c1, c2, c3, out_cat, ...), with the same bits in `out` and `pooled`, but the (b*n, c+4) table [0 | new_xyz | out] stays in
+ * the workgroup's LDS -- it is neither written nor read.  after (b*n,c), skip_max (b*n,w), att (b*n,cb), new_xyz (b*n,3);
+ * ws / wb / wagg packed by pasnl_sa_tail_pack_weights; w0 (c+4,c1: one zero row in front of the reference's 3+c), w1, w2
+ * packed by pasnl_mlp3_pack_weights (all 16-byte aligned).  Covered: w = 9, cb = 32, c = c1 = 128, c2 = 256, c3 = 512 --
+ * anything else is PASNL_EUNSUPPORTED before any launch (the caller runs the two entry points above).  out (b*n,c) is fully
+ * written; pooled: c3 floats per cloud at pooled + cloud * pooled_stride (pooled_stride >= c3; the other columns are NOT
+ * written); workspace: pasnl_mlp3_max_pool_workspace_bytes(b, n, c3) bytes. */
+int pasnl_cls_tail_group_all(int b, int n, int w, int cb, int c, const float* after, const float* skip_max, const float* att,
+                             const float* ws_packed, const float* bs, const float* wb_packed, const float* bb,
+                             const float* wagg_packed, const float* bagg, const float* new_xyz, int c1, int c2, int c3,
+                             const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* out, float* pooled, long pooled_stride, void* workspace, size_t workspace_bytes,
+                             pasnl_stream_t stream);
+
 /* ------------------------------------------------------------------ fp32-grade products on the bf16 matrix pipe (csrc/dense_bf16x3.hip)
  * An explicit MODE (the Python side's tf_util.DENSE_BF16X3; off by default, never used for the headline benchmark):
  * out (rows,n) = act(x (rows,kdim; row stride lda) . w + bias) for the long GEMMs behind tf_util.conv2d over a flattened

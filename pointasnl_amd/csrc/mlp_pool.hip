@@ -17,7 +17,12 @@
 // requested while eight steps multiply (two register sets).  The grid has 4 (n = 128, 32-row tiles) or 8 (n = 512, 64-row tiles) tiles
 // per cloud: more workgroups than CUs, handed out by the dispatcher as CUs become free -- a CU that shares its time with the sampler simply
 // takes fewer tiles.  fp32 MFMA: an exact fmaf chain (another summation order than the vendor GEMM's: parity 1e-5 of scale).
+//
+// tail_group_all_kernel (pasnl_cls_tail_group_all) is layer3_1's form of the same kernel with the classifier's layer 1 tail in
+// front of it: the tile's X rows are not read from a table but computed in place from the tail's inputs (mlp3_tile is the part
+// the two kernels share; the tail's products are sa_tail.hpp's, shared with cells.hip).
 #include "common.hpp"
+#include "sa_tail.hpp"
 
 namespace pasnl {
 
@@ -115,18 +120,55 @@ __device__ __forceinline__ void mp_layer(const float* in, int pin, int K, const 
   }
 }
 
+// the three convolutions of a tile staged in A ([32 RB][pa]: X, then H2; Bf [32 RB][C1 + 1]: H1), behind the barrier that
+// published X: the column maxima of relu(H2 W2 + b2) over the tile's rows go to po[0 .. C3)
+template <int C1, int C2, int C3, int RB>
+__device__ __forceinline__ void mlp3_tile(float* A, int pa, float* Bf, int k0, const float* __restrict__ w0, const float* __restrict__ b0,
+                                          const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+                                          const float* __restrict__ b2, float* __restrict__ po, int wave, int ql, int h) {
+  constexpr int NW = 8, PB = C1 + 1;
+  mp_layer<C1, RB>(A, pa, k0, w0, b0, Bf, PB, wave, ql, h);
+  __syncthreads();
+  mp_layer<C2, RB>(Bf, PB, C1, w1, b1, A, pa, wave, ql, h);
+  __syncthreads();
+  // ---- the last convolution, pooled: column maxima over the tile's rows (max and relu(. + bias) commute)
+  constexpr int NB = C3 / 32 / NW;
+  int loff[NB];
+  mp_f32x16 acc[RB][NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    loff[i] = (h * C3 + (wave + NW * i) * 32 + ql) * 8;
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[rb][i][r] = 0.f;
+  }
+  mp_mm<C3, NB, RB>(A + ql * pa + h, 32 * pa, C2 >> 4, w2, loff, acc);
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    float mx = acc[0][i][0];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[rb][i][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32));  // the other half of the wave holds the other 16 rows
+    const int ch = (wave + NW * i) * 32 + ql;
+    if (h == 0) po[ch] = fmaxf(mx + b2[ch], 0.f);
+  }
+}
+
 template <int C1, int C2, int C3, int RB>
 __global__ __launch_bounds__(512) void mlp3_pool_kernel(int n, int k0, const float* __restrict__ x, const float* __restrict__ w0,
                                                         const float* __restrict__ b0, const float* __restrict__ w1,
                                                         const float* __restrict__ b1, const float* __restrict__ w2,
                                                         const float* __restrict__ b2, float* __restrict__ partial) {
-  constexpr int NW = 8, PB = C1 + 1;
+  constexpr int NW = 8;
   static_assert(C1 % 32 == 0 && C2 % 256 == 0 && C3 % 256 == 0, "blocks of 32 channels; the two wide layers fill all eight waves");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int pa = max((k0 + 15) & ~15, C2) | 1;  // odd row pitch (k0 and C2 are even)
   constexpr int TR = 32 * RB;                 // rows per tile
   float* A = reinterpret_cast<float*>(smem);  // [TR][pa]: X, then H2
-  float* Bf = A + TR * pa;                    // [TR][PB]: H1
+  float* Bf = A + TR * pa;                    // [TR][C1 + 1]: H1
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, ql = lane & 31;
   const int tile = blockIdx.x, cloud = blockIdx.y;
   // ---- the tile's rows (a row beyond the cloud repeats its last point: no maximum changes)
@@ -145,37 +187,116 @@ __global__ __launch_bounds__(512) void mlp3_pool_kernel(int n, int k0, const flo
     }
   }
   __syncthreads();
-  mp_layer<C1, RB>(A, pa, k0, w0, b0, Bf, PB, wave, ql, h);
-  __syncthreads();
-  mp_layer<C2, RB>(Bf, PB, C1, w1, b1, A, pa, wave, ql, h);
-  __syncthreads();
-  // ---- the last convolution, pooled: column maxima over the tile's rows (max and relu(. + bias) commute)
+  mlp3_tile<C1, C2, C3, RB>(A, pa, Bf, k0, w0, b0, w1, b1, w2, b2, partial + ((size_t)cloud * gridDim.x + tile) * C3, wave, ql, h);
+}
+
+// ---- The classifier's layer 1 tail (cells.hip: sa_tail_kernel, w = 9 skip columns, cb = 32, C = 128) in front of layer3_1
+// (mlp 128, 256, 512), one launch: what the tail writes is exactly what the group-all module reads, 64 rows at a time, so the
+// [0 | xyz | out] table never goes through memory (17 MB written and read back per forward of 64 clouds) and the tail's own
+// launch -- a single wave of workgroups whose time is one workgroup's chain of round trips -- disappears.
+// Per 64-row tile of one cloud, eight waves: the rows of after / skip / att are staged TRANSPOSED, two 32-row blocks side by
+// side in the tail's own layout (xs[k * 33 + row]); wave w runs tail stage 1 and then stage 2 for channel block w & 3 of row
+// block w >> 2 through tail_product itself (sa_tail.hpp: bias as the initial accumulator, k in ascending pairs -- the bits of
+// the separate launch); stage 2's D tile goes straight to columns 4.. of the tile's X rows, whose columns 0..3 = [0 | xyz]
+// were staged with the rest; `out` rows are stored from X (coalesced, rows past the cloud masked) and the three convolutions
+// follow as in mlp3_pool_kernel.  A row past the cloud repeats the cloud's last point in EVERY staged table, so its X row
+// repeats the last row and no maximum changes.  LDS: X [64][257] and behind it the tail's tiles, which H1 [64][129] reuses.
+constexpr int TG_C = 128, TG_W = 9, TG_CB = 32, TG_K0 = TG_C + 4, TG_C2 = 256, TG_C3 = 512, TG_TR = 64;
+constexpr int TG_PA = (((TG_K0 + 15) & ~15) > TG_C2 ? ((TG_K0 + 15) & ~15) : TG_C2) | 1;
+constexpr int TG_TAIL_FLOATS = 2 * (TG_C + 32 + 32) * 33;  // V^T, S^T, N^T of two row blocks (S and N padded to 32 channels)
+constexpr int TG_H1_FLOATS = TG_TR * (TG_C + 1);
+constexpr size_t TG_LDS_BYTES = ((size_t)TG_TR * TG_PA + (TG_TAIL_FLOATS > TG_H1_FLOATS ? TG_TAIL_FLOATS : TG_H1_FLOATS)) * sizeof(float);
+static_assert(TG_LDS_BYTES <= LDS_MAX_BYTES, "X rows + the tail's tiles fit one workgroup's LDS");
+static_assert(TG_W <= 2 * TAIL_KS && TG_CB == 2 * TAIL_KS && TG_C % 64 == 0 && TG_C / 32 * 2 == 8, "one (channel block, row block) per wave");
+
+__global__ __launch_bounds__(512) void tail_group_all_kernel(int n, const float* __restrict__ after, const float* __restrict__ S,
+                                                             const float* __restrict__ N, const float* __restrict__ Ws,
+                                                             const float* __restrict__ bs, const float* __restrict__ Wb,
+                                                             const float* __restrict__ bb, const float* __restrict__ Wagg,
+                                                             const float* __restrict__ bagg, const float* __restrict__ xyz3,
+                                                             const float* __restrict__ w0, const float* __restrict__ b0,
+                                                             const float* __restrict__ w1, const float* __restrict__ b1,
+                                                             const float* __restrict__ w2, const float* __restrict__ b2,
+                                                             float* __restrict__ out, float* __restrict__ partial) {
+  constexpr int C = TG_C, pa = TG_PA, RPW = TG_TR / 8;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* A = reinterpret_cast<float*>(smem);  // [64][pa]: X = [0 | xyz | O | zeros to 144], then H2
+  float* Bf = A + TG_TR * pa;                 // the tail's tiles, then H1 [64][C + 1]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l32 = lane & 31;
+  const int tile = blockIdx.x, cloud = blockIdx.y;
+  const long cloud0 = (long)cloud * n;
+  const int rb = wave >> 2;                    // the row block this wave stages 8 rows of -- and computes a channel block of
+  float* vt = Bf + rb * (C * 33);              // [C][33]   V^T of the row block
+  float* st = Bf + 2 * C * 33 + rb * (32 * 33);        // [32][33]  S^T, zero beyond w
+  float* nt_ = Bf + 2 * (C + 32) * 33 + rb * (32 * 33);  // [32][33]  N^T
+  // ---- the tile's rows, every request before the first write (one round trip); lanes 0-31 take S, lanes 32-63 take N
   {
-    constexpr int NB = C3 / 32 / NW;
-    int loff[NB];
-    mp_f32x16 acc[RB][NB];
+    float v[3][RPW], cx[RPW];
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      loff[i] = (h * C3 + (wave + NW * i) * 32 + ql) * 8;
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[rb][i][r] = 0.f;
+    for (int i = 0; i < RPW; ++i) {
+      const long row = cloud0 + min(tile * TG_TR + wave * RPW + i, n - 1);
+      v[0][i] = after[row * C + lane];
+      v[1][i] = after[row * C + 64 + lane];
+      v[2][i] = h ? N[row * TG_CB + l32] : S[row * TG_W + min(l32, TG_W - 1)];
+      cx[i] = xyz3[row * 3 + max(min(lane, 3) - 1, 0)];
     }
-    mp_mm<C3, NB, RB>(A + ql * pa + h, 32 * pa, C2 >> 4, w2, loff, acc);
-    float* po = partial + ((size_t)cloud * gridDim.x + tile) * C3;
+    __builtin_amdgcn_sched_barrier(0);
+    const int rr0 = (wave & 3) * RPW;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      float mx = acc[0][i][0];
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, acc[rb][i][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));  // the other half of the wave holds the other 16 rows
-      const int ch = (wave + NW * i) * 32 + ql;
-      if (h == 0) po[ch] = fmaxf(mx + b2[ch], 0.f);
+    for (int i = 0; i < RPW; ++i) {
+      vt[lane * 33 + rr0 + i] = v[0][i];
+      vt[(64 + lane) * 33 + rr0 + i] = v[1][i];
+      (h ? nt_ : st)[l32 * 33 + rr0 + i] = (h || l32 < TG_W) ? v[2][i] : 0.f;
+      float* xr = A + (wave * RPW + i) * pa;
+      if (lane < 4) xr[lane] = lane ? cx[i] : 0.f;
+      else if (lane < 4 + ((TG_K0 + 15) & ~15) - TG_K0) xr[TG_K0 + lane - 4] = 0.f;  // layer 0 contracts to a multiple of 16
     }
   }
+  __syncthreads();
+  const int cbase = (wave & 3) * 32;
+  // ---- tail stage 1: V^T += relu(Ws^T S^T + bs) + relu(Wb^T N^T + bb)
+  {
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = bs[cbase + kappa(i, h)];
+    acc = tail_product(TailW<true>{Ws, C, TG_W, h, cbase + l32}, st, l32, acc);
+    f32x16 v;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = fmaxf(acc[i], 0.f);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = bb[cbase + kappa(i, h)];
+    acc = tail_product(TailW<true>{Wb, C, TG_CB, h, cbase + l32}, nt_, l32, acc);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] += fmaxf(acc[i], 0.f);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float* cell = vt + (cbase + kappa(i, h)) * 33 + l32;
+      *cell = *cell + v[i];
+    }
+  }
+  __syncthreads();
+  // ---- tail stage 2: O^T = relu(Wagg^T V^T + bagg), the lane's 16 channels of row l32 straight into the tile's X row
+  {
+    f32x16 o;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[i] = bagg[cbase + kappa(i, h)];
+    o = tail_product(TailW<true>{Wagg, C, C, h, cbase + l32}, vt, l32, o);
+    float* xr = A + (rb * 32 + l32) * pa + 4 + cbase;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) xr[kappa(i, h)] = fmaxf(o[i], 0.f);
+  }
+  __syncthreads();  // X is complete, and every wave has read V^T: H1 may overwrite the tail's tiles
+  // ---- the layer's output rows (128-byte pieces; the stores drain behind layer 0's products)
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) {
+    const int r = wave * RPW + i, row = tile * TG_TR + r;
+    if (row < n) {
+      float* o = out + (cloud0 + row) * C;
+      o[lane] = A[r * pa + 4 + lane];
+      o[64 + lane] = A[r * pa + 4 + 64 + lane];
+    }
+  }
+  mlp3_tile<TG_C, TG_C2, TG_C3, 2>(A, pa, Bf, TG_K0, w0, b0, w1, b1, w2, b2, partial + ((size_t)cloud * gridDim.x + tile) * TG_C3, wave, l32, h);
 }
 
 // W (K, N) row-major -> P[bt][h][n][u] = W[16 bt + 2 u + h][n] (zero beyond K): one thread per 16-byte piece
@@ -256,4 +377,28 @@ extern "C" int pasnl_mlp3_max_pool(int b, int n, int k0, int c1, int c2, int c3,
   if (rc != PASNL_OK) return rc;
   // maxima over the tiles of a cloud -> out[cloud * out_stride + channel]
   return pasnl_max_pool_rows_strided(b, (n + tr - 1) / tr, c3, partial, out, out_stride, stream);
+}
+
+extern "C" int pasnl_cls_tail_group_all(int b, int n, int w, int cb, int c, const float* after, const float* skip_max, const float* att,
+                                        const float* ws_packed, const float* bs, const float* wb_packed, const float* bb,
+                                        const float* wagg_packed, const float* bagg, const float* new_xyz, int c1, int c2, int c3,
+                                        const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                                        const float* b2, float* out, float* pooled, long pooled_stride, void* workspace,
+                                        size_t workspace_bytes, pasnl_stream_t stream) {
+  PASNL_REQUIRE(b >= 0 && n > 0 && w > 0 && cb > 0 && c > 0 && c1 > 0 && c2 > 0 && c3 > 0 && pooled_stride >= c3, PASNL_EINVAL);
+  if (b == 0) return PASNL_OK;
+  PASNL_REQUIRE(after && skip_max && att && ws_packed && bs && wb_packed && bb && wagg_packed && bagg && new_xyz, PASNL_ENULL);
+  PASNL_REQUIRE(w0 && b0 && w1 && b1 && w2 && b2 && out && pooled && workspace, PASNL_ENULL);
+  PASNL_REQUIRE(workspace_bytes >= pasnl_mlp3_max_pool_workspace_bytes(b, n, c3), PASNL_EWORKSPACE);
+  PASNL_REQUIRE(w == TG_W && cb == TG_CB && c == TG_C && c1 == TG_C && c2 == TG_C2 && c3 == TG_C3, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(b <= 65535, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE((reinterpret_cast<uintptr_t>(ws_packed) | reinterpret_cast<uintptr_t>(wb_packed) | reinterpret_cast<uintptr_t>(wagg_packed) |
+                 reinterpret_cast<uintptr_t>(w0) | reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) % 16 == 0,
+                PASNL_EUNSUPPORTED);  // (packed weights: read in 16-byte pieces)
+  const int tiles = (n + TG_TR - 1) / TG_TR;
+  if (launch(tail_group_all_kernel, dim3(tiles, b), dim3(512), TG_LDS_BYTES, pasnl_hip_stream(stream), n, after, skip_max, att, ws_packed,
+             bs, wb_packed, bb, wagg_packed, bagg, new_xyz, w0, b0, w1, b1, w2, b2, out, static_cast<float*>(workspace)) != PASNL_OK)
+    return PASNL_ELAUNCH;
+  if (pasnl_launch_status() != PASNL_OK) return PASNL_ELAUNCH;
+  return pasnl_max_pool_rows_strided(b, tiles, c3, static_cast<const float*>(workspace), pooled, pooled_stride, stream);
 }

@@ -4,7 +4,7 @@ weights live in the active tf_util.VariableStore (seeded; there are no checkpoin
 """
 import torch
 
-from pointasnl_amd.utils import tf_util
+from pointasnl_amd.utils import tf_util, pointasnl_util
 from pointasnl_amd.utils.pointnet_util import pointnet_sa_module
 from pointasnl_amd.utils.pointasnl_util import PointASNLSetAbstraction, get_repulsion_loss, sa_search, Forked
 
@@ -37,6 +37,14 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     end_points['l0_xyz'] = l0_xyz
     as_neighbor = [12, 12] if adaptive_sample else [0, 0]
 
+    # the two pooled vectors are written side by side into fc1's input: tf.concat([l3_points, l3_points_res]) for free
+    # (allocated up here: layer 1's last kernel runs layer3_1 on its own rows where it can -- `group_all` below)
+    net = torch.empty((batch_size, 1024 + 512), dtype=torch.float32, device=point_cloud.device)
+    # with adaptive sampling the fused launch measured 0.5 % SLOWER per step (EXPERIMENTS.md, "Layer 1's tail inside layer3_1's
+    # kernel"; supposed, not traced: layer 2's search is forked inside the forward there and now waits behind layer3_1's tiles):
+    # two launches unless asked for
+    fuse3_1 = not adaptive_sample or pointasnl_util.SA_TAIL_GROUP_ALL == "always"
+
     # Set abstraction layers.  Layer 2's search (FPS + kNN) reads layer 1's sampled coordinates only, so it is forked onto
     # a side stream the moment those are final and runs beside layer 1's MFMA / GEMM work (pointasnl_util.Forked)
     search2 = []
@@ -46,6 +54,7 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     l1_xyz, l1_points = PointASNLSetAbstraction(l0_xyz, l0_points, npoint=512, nsample=32, mlp=[64, 64, 128],
                                                 is_training=is_training, bn_decay=bn_decay, weight_decay=weight_decay,
                                                 scope='layer1', as_neighbor=as_neighbor[0], search=search, xyz_concat=True,
+                                                group_all=dict(mlp=[128, 256, 512], scope='layer3_1', pooled_out=net[:, 1024:]) if fuse3_1 else None,
                                                 after_sampling=None if search2 else lambda xyz1: search2.append(
                                                     Forked(lambda: sa_search(xyz1, None, 128, 64), lazy=lazy_fork)))
     end_points['l1_xyz'] = l1_xyz
@@ -57,11 +66,10 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     end_points['l2_xyz'] = l1_xyz  # sic: the reference stores l1_xyz here (pointasnl_cls.py:38)
     if before_head is not None and fork_at == "head":
         before_head()
-    # the two pooled vectors are written side by side into fc1's input: tf.concat([l3_points, l3_points_res]) for free
-    net = torch.empty((batch_size, 1024 + 512), dtype=torch.float32, device=point_cloud.device)
-    _, l3_points_res, _ = pointnet_sa_module(l1_xyz, l1_points, npoint=None, radius=None, nsample=None,
-                                             mlp=[128, 256, 512], mlp2=None, group_all=True, is_training=is_training,
-                                             bn_decay=bn_decay, scope='layer3_1', pooled_out=net[:, 1024:])
+    if getattr(l1_points, "group_all_pooled", None) is None:  # (else layer 1's last kernel ran layer3_1 as well: net[:, 1024:] is written)
+        _, l3_points_res, _ = pointnet_sa_module(l1_xyz, l1_points, npoint=None, radius=None, nsample=None,
+                                                 mlp=[128, 256, 512], mlp2=None, group_all=True, is_training=is_training,
+                                                 bn_decay=bn_decay, scope='layer3_1', pooled_out=net[:, 1024:])
     _, l3_points, _ = pointnet_sa_module(l2_xyz, l2_points, npoint=None, radius=None, nsample=None,
                                          mlp=[256, 512, 1024], mlp2=None, group_all=True, is_training=is_training,
                                          bn_decay=bn_decay, scope='layer3_2', pooled_out=net[:, :1024])

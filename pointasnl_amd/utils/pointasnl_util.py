@@ -17,7 +17,7 @@ import torch
 from pointasnl_amd import _hip
 from pointasnl_amd import tf_sampling, tf_grouping, nearest_neighbors
 from pointasnl_amd.tf_interpolate import three_nn, three_interpolate, three_weights, fp_interpolate_cat
-from pointasnl_amd.utils import tf_util
+from pointasnl_amd.utils import tf_util, pointnet_util
 
 NL_KEY_PARTS = True  # nl_attention: keys over workgroups where the query tiles alone leave CUs empty (pasnl_nl_attention_ws)
 NL_VARIANT = 0  # 0 auto / 1 vector-FMA / 2 MFMA  (pasnl_nl_attention); bench.py --ops sweeps it
@@ -94,6 +94,8 @@ SA_TAIL_MIN_ROWS = 2048
 FP_HEAD_FUSED = True     # PointASNLDecodingLayer (inference, no autograd): three_weights + three_interpolate as one kernel
 SA_CELL_PACKED = True    # the wide cells (one workgroup per group, weights from L2) get their matrices packed in operand order too
 SA_TAIL_PACKED = True    # pasnl_sa_tail with its weights packed in operand order (16-byte weight loads)
+SA_TAIL_GROUP_ALL = True  # the classifier's layer 1: tail + the layer3_1 group_all module in one launch (pasnl_cls_tail_group_all) where it was
+                          # measured faster -- without adaptive sampling; "always": with it too (0.5 % slower there); False = two launches (A/B)
 SA_TAIL_FUSED = True     # skip conv + back-projection + adds + aggregation in one kernel (pasnl_sa_tail); False = op by op
 SA_CELL_GATHER = True    # grouping fused into the local cell (pasnl_sa_cell); False = pasnl_sa_group + pasnl_sa_local_cell
 SA_CELL_SINGLE = True     # mlp = [c, c] (one convolution, c = 32 / 64 / 128): no conv1 at all instead of an identity conv1 (False: A/B)
@@ -740,7 +742,7 @@ def _tail_packed(st, w):
 
 def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_decay, weight_decay, scope, bn=True,
                             use_knn=True, radius=None, as_neighbor=8, NL=True, search=None, after_sampling=None,
-                            xyz_concat=False, after_cell=None, before_after_conv=None, residual=None):
+                            xyz_concat=False, after_cell=None, before_after_conv=None, residual=None, group_all=None):
     '''Mirror of pointasnl_util.py:221-292: one PointASNL set-abstraction layer.
         xyz (B,N,3), feature (B,N,C)  ->  new_xyz (B,npoint,3), new_points (B,npoint,mlp[-1])
     npoint points are sampled (FPS) and moved by AdaptiveSampling over their first `as_neighbor` neighbours; each keeps
@@ -752,7 +754,18 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
     layer's last kernel then writes those rows as well, and the returned new_points carries them as `.xyz_concat`
     = (new_xyz, (B,npoint,4+C) table [0 | xyz | points]) for pointnet_util.sample_and_group_all to pick up.
     residual: (B,npoint,mlp[-1]) added to the layer's output -- the `_res` model's "l1_2_points + l1_1_points"
-    (pointasnl_sem_seg_res.py:37,42,47,52) in the epilogue of the layer's last kernel instead of a pass of its own.'''
+    (pointasnl_sem_seg_res.py:37,42,47,52) in the epilogue of the layer's last kernel instead of a pass of its own.
+    group_all: dict(mlp=, scope=, pooled_out=) -- the group_all module pointnet_sa_module(new_xyz, new_points, mlp=..., scope=...,
+    pooled_out=...) the caller runs on this layer's output next (pointasnl_cls layer3_1).  Where the layer's tail and that module
+    fit one kernel (pasnl_cls_tail_group_all: inference, 9 skip columns, 32 attention channels, 128 -> [128, 256, 512]) they
+    run as one launch, the pooled vectors are in pooled_out on return and new_points carries `.group_all_pooled` = that
+    (B, mlp[-1]) view: the caller skips the module.  Otherwise nothing changes (xyz_concat still applies).'''
+    ga_weights = None
+    if (group_all is not None and SA_TAIL_GROUP_ALL and SA_TAIL_FUSED and SA_TAIL_PACKED and NL and residual is None and not is_training
+            and mlp[-1] == 128 and tuple(group_all['mlp']) == (128, 256, 512)):
+        # the module's variables are named by ITS scope path, not by this layer's: resolved out here
+        with tf_util.variable_scope(group_all['scope']):
+            ga_weights = pointnet_util.group_all_weights(group_all['mlp'], 3 + mlp[-1], 1, bn)
     with tf_util.variable_scope(scope):
         batch_size, num_points, num_channel = feature.shape
         # Farthest point sampling + neighbour search (the reference's sampling() / grouping(): pointasnl_util.py:236-242);
@@ -876,6 +889,19 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
                     # the three matrices in the matrix instruction's operand order, packed once per variable
                     pk = [_tail_packed(st, m) if m is not None else None for m in (ws, wb if NL else None, wagg)]
                     cat = None
+                    if ga_weights is not None and (int(w_in), int(cb)) == (9, 32) and new_xyz.shape[1] == npoint:
+                        # tail + the caller's group_all module: one launch, no [0 | xyz | out] table
+                        new_xyz = new_xyz.contiguous()
+                        gmlp = group_all['mlp']
+                        pooled = pointnet_util.group_all_pooled(group_all.get('pooled_out'), batch_size, gmlp[-1], xyz.device)
+                        wsb = pointnet_util.group_all_workspace(batch_size, npoint, gmlp[-1], xyz.device)
+                        _hip.launch("pasnl_cls_tail_group_all", "sa_tail_group_all", batch_size, npoint, int(w_in), int(cb), int(c_out),
+                                    *args[4:7], _hip.ptr(pk[0]), args[8], _hip.ptr(pk[1]), args[10], _hip.ptr(pk[2]), args[12],
+                                    _hip.ptr(new_xyz), gmlp[0], gmlp[1], gmlp[2], *[_hip.ptr(t) for t in ga_weights], args[13],
+                                    _hip.ptr(pooled), ctypes.c_long(pooled.stride(0) if batch_size > 1 else gmlp[-1]),
+                                    _hip.ptr(wsb), ctypes.c_size_t(wsb.numel()))
+                        out.group_all_pooled = pooled
+                        return new_xyz, out
                     if xyz_concat and XYZ_CONCAT:
                         new_xyz = new_xyz.contiguous()
                         cat = torch.empty((batch_size, npoint, 4 + c_out), dtype=torch.float32, device=xyz.device)

@@ -61,17 +61,12 @@ GROUP_ALL_FUSED = (128,)
 _GROUP_ALL_WS = {}
 
 
-def group_all_mlp_max(new_points, mlp, bn, pooled_out=None):
-    """The body of a group_all module (pointnet_util.py:123-137) in one launch (csrc/mlp_pool.hip): the three [1,1] convolutions
-    of `mlp` (BN folded, ReLU) over all n points of every cloud and the maximum over the points.
-    new_points (B,1,n,kp) [with `.input_pad` leading alignment columns the reference's tensor does not have] -> (B,1,1,mlp[-1]);
-    the variables are the ones conv2d would create (scopes conv0..2).  Raises PasnlUnsupported outside the kernel's shapes."""
-    b, one, n, kp = new_points.shape
-    if one != 1 or len(mlp) != 3:
-        raise _hip.PasnlUnsupported("group_all_mlp_max: one group per cloud, three convolutions")
-    pad = getattr(new_points, "input_pad", 0)
+def group_all_weights(mlp, cin, pad, bn):
+    """[w0, b0, w1, b1, w2, b2] of a group_all module's three convolutions at the current scope (conv0..2, the variables conv2d
+    would create), BN folded, the matrices in the matrix instruction's operand order (pasnl_mlp3_pack_weights), packed once.
+    pad: leading alignment columns of the input rows the reference's tensor does not have -- zero rows in front of w0."""
     st = tf_util.store()
-    cin, ws = kp - pad, []
+    ws = []
     for i, c in enumerate(mlp):
         with tf_util.variable_scope('conv%d' % i):
             w, bb = st.layer(cin, c, bn)
@@ -91,22 +86,44 @@ def group_all_mlp_max(new_points, mlp, bn, pooled_out=None):
             w = st._folded[key][0]
         ws += [w, bb]
         cin = c
+    return ws
+
+
+def group_all_pooled(pooled_out, b, c3, device):
+    """the (B, C) float32 view a group_all kernel writes its maxima to: `pooled_out` checked, or a new tensor"""
+    if pooled_out is None:
+        return torch.empty((b, c3), dtype=torch.float32, device=device)
+    if tuple(pooled_out.shape) != (b, c3) or pooled_out.stride(1) != 1 or pooled_out.dtype != torch.float32:
+        raise ValueError("group_all_mlp_max: pooled_out must be a (B, C) float32 view with unit column stride")
+    return pooled_out
+
+
+def group_all_workspace(b, n, c3, device):
+    """the tile maxima's buffer: grow-only, per stream (a captured graph keeps the buffer it was captured with)"""
+    nbytes = int(_hip.lib().pasnl_mlp3_max_pool_workspace_bytes(b, n, c3))
+    key = (device.index, torch.cuda.current_stream().cuda_stream, c3)
+    bufs = _GROUP_ALL_WS.setdefault(key, [])
+    if not bufs or bufs[-1].numel() < nbytes:
+        bufs.append(torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device))
+    return bufs[-1]
+
+
+def group_all_mlp_max(new_points, mlp, bn, pooled_out=None):
+    """The body of a group_all module (pointnet_util.py:123-137) in one launch (csrc/mlp_pool.hip): the three [1,1] convolutions
+    of `mlp` (BN folded, ReLU) over all n points of every cloud and the maximum over the points.
+    new_points (B,1,n,kp) [with `.input_pad` leading alignment columns the reference's tensor does not have] -> (B,1,1,mlp[-1]);
+    the variables are the ones conv2d would create (scopes conv0..2).  Raises PasnlUnsupported outside the kernel's shapes."""
+    b, one, n, kp = new_points.shape
+    if one != 1 or len(mlp) != 3:
+        raise _hip.PasnlUnsupported("group_all_mlp_max: one group per cloud, three convolutions")
+    pad = getattr(new_points, "input_pad", 0)
+    ws = group_all_weights(mlp, kp - pad, pad, bn)
     x = new_points.reshape(b, n, kp)
     if not x.is_contiguous():
         x = x.contiguous()
     c3 = mlp[-1]
-    if pooled_out is None:
-        out2d = torch.empty((b, c3), dtype=torch.float32, device=x.device)
-    else:
-        if tuple(pooled_out.shape) != (b, c3) or pooled_out.stride(1) != 1 or pooled_out.dtype != torch.float32:
-            raise ValueError("group_all_mlp_max: pooled_out must be a (B, C) float32 view with unit column stride")
-        out2d = pooled_out
-    nbytes = int(_hip.lib().pasnl_mlp3_max_pool_workspace_bytes(b, n, c3))
-    key = (x.device.index, torch.cuda.current_stream().cuda_stream, c3)
-    bufs = _GROUP_ALL_WS.setdefault(key, [])  # grow-only, per stream: a captured graph keeps the buffer it was captured with
-    if not bufs or bufs[-1].numel() < nbytes:
-        bufs.append(torch.empty(max(nbytes, 256), dtype=torch.uint8, device=x.device))
-    wsb = bufs[-1]
+    out2d = group_all_pooled(pooled_out, b, c3, x.device)
+    wsb = group_all_workspace(b, n, c3, x.device)
     _hip.launch("pasnl_mlp3_max_pool", "mlp3_max_pool", b, n, kp, mlp[0], mlp[1], mlp[2], _hip.ptr(x), *[_hip.ptr(t) for t in ws],
                 _hip.ptr(out2d), ctypes.c_long(out2d.stride(0) if b > 1 else c3), _hip.ptr(wsb), ctypes.c_size_t(wsb.numel()))
     return out2d.unflatten(0, (b, 1)).unsqueeze(2)
