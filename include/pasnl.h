@@ -718,6 +718,48 @@ int pasnl_scene_labels(long m, const int* proj, const float* probs, int nc, cons
 int pasnl_confusion_matrix(long n, const int* targets, const int* preds, const int* label_values, int nl, long long* out,
                            pasnl_stream_t stream);
 
+/* ---- The grid training input loops on the device (csrc/grid_train.hip): the `'training'` split of get_batch_gen in
+ * ScanNet/scannet_dataset_grid.py (D) :435-549 and SemanticKITTI/semantic_kitti_dataset_grid.py (K) :193-292, and
+ * `tf_augment_input` with the colour drop (D:551-645, K:294-354).  The pick, crop, order and potential update are the test
+ * loops' entries above; the tallies of train_scannet_grid.py:264-302 and train_semantic_kitti_grid.py:224-263 are
+ * pasnl_block_train_score.  None of the three entries synchronises with the host. */
+
+/* The descriptors of b crops whose scan and pick the host drew (K:216-221: `cloud_ind = i`,
+ * `pick_idx = np.random.choice(len(pc), 1)`): desc[c] = {offset = offsets[cloud[c]], cloud[c], pick[c], n, k[c], centre =
+ * points[offset + pick[c]]} over s scans.  cloud: b ints in HOST memory (the generator's scan order is the host's; they
+ * travel as kernel arguments, so a captured launch holds the ones it was captured with), one outside [0, s) -> PASNL_EINVAL;
+ * pick, k: b DEVICE ints each (staged draws).  A pick outside its scan writes n = 0, an empty crop (the caller checks its
+ * picks before it stages them). */
+int pasnl_scan_pick_given(int b, int s, const long long* offsets, const float* points, const int* cloud, const int* pick,
+                          const int* k, pasnl_scan_crop_t* desc, pasnl_stream_t stream);
+
+/* The labels and sample weights of b crops (D:525-531, K:222, 237-239): out_labels[c][j] = labels[offsets[cloud[c]] +
+ * select[c][j]] with labels the flat (N,) i32 class indices beside the flat points, cloud (b) i32 on the device, select
+ * (b,num_point) i32 indices into each crop's scan; out_weights[c][j] = weights[out_labels[c][j]], weights (nw) f32.  A label
+ * outside [0, nw) is written as it is with weight 0 (the callers check the range once, where the reference would raise
+ * IndexError).  weights == NULL: all-zero weights (the validation split, D:528-529).  b <= 65535.  One launch. */
+int pasnl_scan_train_labels(int b, int num_point, const int* select, const int* cloud, const long long* offsets, const int* labels,
+                            const float* weights, int nw, int* out_labels, float* out_weights, pasnl_stream_t stream);
+
+/* tf_augment_input and the colour drop (D:586-645 with D:564-568, K:304-354) of b crops of (num_point, width) f32 rows, src ->
+ * dst (src == dst allowed), one launch, one thread per point.  rotation: 1 'vertical', 0 'none' (else PASNL_EINVAL); scale_min <=
+ * scale_max; anisotropic; sym_x, sym_y, sym_z; noise >= 0 (the stddev); color (the keep probability): columns 3..5 are
+ * multiplied by keep when width >= 6, every further column is copied; width >= 3, b <= 65535.
+ * Random numbers are Philox4x32-10 words: key (seed lo, seed hi), counter (j, item lo, item hi, stream), item = item0[0] + c
+ * (item0: ONE device unsigned long long, the running number of the batch's first crop; seed: a host value); a uniform is u =
+ * (w >> 8) * 2^-24 in [0,1).  Stream 0, per crop: j = 0 -> u_theta, u_sx, u_sy, u_sz; j = 1 -> u_symx, u_symy, u_symz, u_colour.
+ * theta = u_theta * f32(2 pi); cos, sin = f32 of the double cosine and sine of (double)theta; s_i = scale_min + u_si *
+ * (scale_max - scale_min), each operation rounded to f32 (u_sx for all axes unless anisotropic), negated where the axis'
+ * symmetry is on and not (u_sym > 0.5) -- tf.round(u) * 2 - 1; keep = u_colour < color.  Stream 1, per point j: Box-Muller
+ * normals in f32, (x, y) from words (0, 1) and z from words (2, 3) (its second value dropped): r = sqrt(-2 log(((wa >> 8) + 1)
+ * * 2^-24)), (r cos, r sin)(2 pi (wb >> 8) 2^-24).  Then, in f32 with no contraction: x' = (x*c) + (y*s), y' = (y*c) - (x*s),
+ * z' = z ('none': x' = x, y' = y); out_i = x'_i * s_i + f32(noise * normal_i).  TF's own generator and the summation order of
+ * its matmul are not reproduced.  out_params (b,8) f32: theta, cos, sin, s0, s1, s2, keep, 0 ('none': 0, 1, 0); out_noise
+ * (b,num_point,3) f32: the unit normals; either may be NULL. */
+int pasnl_scan_augment(int b, int num_point, int width, const float* src, float* dst, int rotation, float scale_min, float scale_max,
+                       int anisotropic, int sym_x, int sym_y, int sym_z, float noise, float color, unsigned long long seed,
+                       const unsigned long long* item0, float* out_params, float* out_noise, pasnl_stream_t stream);
+
 /* ---- The ScanNet sliding-window whole-scene test loop on the device (ScanNet/scannet_dataset.py (D) :183-300
  * `ScannetDatasetWholeSceneSlidingWindow.__getitem__`, ScanNet/test_scannet.py (T) :96-103 `add_vote` and :107-196
  * `eval_one_epoch`).  One scene at a time: xyz (n,3) f32 is the scene's OWN buffer, moved in place vote after vote as the

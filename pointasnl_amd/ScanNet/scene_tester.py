@@ -17,6 +17,9 @@ num_point + num_buffer + num_buffer // 4 - 1 points (9 471 at the defaults): a s
 data_rep's np.random.choice into a stream whose length depends on the device-chosen scene.  Whether real ScanNet scenes at
 the reference's sub-sampling always clear that count has not been measured.
 
+`SceneCrops` is the part every split shares -- the scenes, the potentials, the draws and the crop chain; `SceneTester` adds
+the votes, and `scene_trainer.SceneTrainer` the training split's labels, weights and augmentation.
+
 Deviations: the crops are fed unaugmented (the reference maps tf_augment_input over them with TF's RNG, which cannot be
 reproduced; its colour drop is a no-op at augment_color = 1.0); the softmax of a vote is computed here in float32, not by
 TensorFlow; proj_inds computed here break distance ties by the lowest index (sklearn: by its tree's order); PLY and txt
@@ -36,41 +39,16 @@ DESC_BYTES = 48  # sizeof(pasnl_scene_crop_t)
 SMOOTH = {"test": 0.98, "validation": 0.95}  # T:101, 234
 
 
-class SceneTester:
-    """`SceneTester(scenes, colors=colors, num_classes=21, num_point=8192, num_buffer=1024, batch_size=4, split='test',
-    validation_size=500, label_values=np.arange(21), ignored_labels=(0,), with_rgb=True, rng=np.random)`.
+class SceneCrops:
+    """What the grid generator does for every split (D:464-541): the scenes in one flat device buffer with their colours and
+    potentials, the host's draws of a batch and the device chain of its crops.  `SceneTester` adds the votes of the test and
+    validation splits, `scene_trainer.SceneTrainer` the labels, weights and augmentation of the training split."""
 
-    scenes: a list of (n_i,3) float32 sub-sampled scenes (numpy arrays or device tensors) in the order of the reference's
-    input_trees[split]; colors: their (n_i,3) float32 colour rows (with_rgb).  The model sees C = num_classes logits and the
-    tables hold C - 1 classes (T:95, 108); label_values lists every label, ignored ones included, so
-    C - 1 + len(ignored_labels) == len(label_values).  Construction draws `rng.rand(n_i) * 1e-3` scene after scene
-    (D:472-478); every crop then draws `rng.normal(scale=0.35, size=(1, 3))`, `rng.randint(0, num_buffer // 4)` and
-    `rng.shuffle` of its k indices.  abs_coords: append the reference's three extra feature columns float32(xyz + pick)
-    (D:539) to the model input."""
-
-    def __init__(self, scenes, colors=None, num_classes=21, num_point=8192, num_buffer=1024, batch_size=4, split="test",
-                 validation_size=500, label_values=None, ignored_labels=(0,), with_rgb=True, rng=np.random, in_radius=0.0,
-                 abs_coords=False, test_smooth=None):
-        if in_radius > 0:
-            raise NotImplementedError("SceneTester covers the k form only (in_radius == 0): the radius form's shuffle length is "
-                                      "known on the device alone")
-        if split not in SMOOTH:
-            raise ValueError('split must be "test" or "validation"')
-        _hip.require_device()
-        self.S, self.B, self.C, self.split = len(scenes), int(batch_size), int(num_classes), split
-        self.num_point, self.num_buffer, self.validation_size, self.rng = int(num_point), int(num_buffer), int(validation_size), rng
-        self.test_smooth = SMOOTH[split] if test_smooth is None else float(test_smooth)
+    def _init_crops(self, scenes, colors, num_point, num_buffer, batch_size, steps, with_rgb, rng, abs_coords):
+        self.S, self.B = len(scenes), int(batch_size)
+        self.num_point, self.num_buffer, self.rng = int(num_point), int(num_buffer), rng
         self.abs_coords = bool(abs_coords)
-        self.label_values = np.arange(self.C, dtype=np.int32) if label_values is None else np.asarray(label_values, np.int32).reshape(-1)
-        self.ignored_labels = tuple(int(v) for v in ignored_labels)
-        self.ignored_mask = np.isin(self.label_values, self.ignored_labels).astype(np.int32)
-        self.L, self.nc = int(self.label_values.size), self.C - 1
-        if len(set(self.label_values.tolist())) != self.L:
-            raise ValueError("label_values must be distinct")
-        if self.nc < 1 or self.nc + int(self.ignored_mask.sum()) != self.L:
-            raise ValueError(f"num_classes - 1 = {self.nc} table columns + {int(self.ignored_mask.sum())} ignored labels != "
-                             f"{self.L} label values")
-        if self.S < 1 or self.B < 1 or self.validation_size < 1:
+        if self.S < 1 or self.B < 1 or int(steps) < 1:
             raise ValueError("at least one scene, one crop per batch and one batch per epoch")
         if self.num_buffer // 4 < 1:
             raise ValueError("num_buffer // 4 must be >= 1 (the crop draws randint(0, num_buffer // 4))")
@@ -110,9 +88,8 @@ class SceneTester:
             mins.append(float(np.min(pots[-1])))
         self.potentials = torch.from_numpy(np.concatenate(pots)).to(self.device)
         self.min_pots = torch.tensor(mins, dtype=torch.float64, device=self.device)
-        self.probs = torch.zeros((self.N, self.nc), dtype=torch.float32, device=self.device)
         self.win = torch.empty((self.nmax,), dtype=torch.int32, device=self.device)
-        _hip.launch("pasnl_scan_scratch_init", "SceneTester", ctypes.c_long(self.nmax), _p(self.win))
+        _hip.launch("pasnl_scan_scratch_init", type(self).__name__, ctypes.c_long(self.nmax), _p(self.win))
         self.desc = torch.zeros((self.B, DESC_BYTES), dtype=torch.uint8, device=self.device)
         self.idx = torch.empty((self.kcap,), dtype=torch.int32, device=self.device)
         self.d2 = torch.empty((self.kcap,), dtype=torch.float64, device=self.device)
@@ -122,11 +99,6 @@ class SceneTester:
         self.noise_stage = torch.empty((self.B, 3), dtype=torch.float64, device=self.device)
         self.k_stage = torch.empty((self.B,), dtype=torch.int32, device=self.device)
         self.perm_stage = torch.empty((self.B, self.num_point), dtype=torch.int32, device=self.device)
-        self.smooth_old = float(np.float32(self.test_smooth))      # numpy: python_float * float32_array -> float32 product
-        self.smooth_new = float(np.float32(1 - self.test_smooth))
-        self.labels_dev = torch.from_numpy(self.label_values).to(self.device)
-        self.ignored_dev = torch.from_numpy(self.ignored_mask).to(self.device)
-        self.checkpoints = []  # (epoch, new_min) of every checkpoint run() fired
 
     # ---- one batch
     def draw_batch(self):
@@ -178,6 +150,60 @@ class SceneTester:
         self.stage(self.draw_batch())
         return self.enqueue()
 
+    # ---- state
+    def _rows(self, i):
+        return slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
+
+    def potentials_of(self, i):
+        return self.potentials[self._rows(i)]
+
+    def min_potentials(self):
+        return self.min_pots.cpu().numpy()
+
+    def scene_points(self, i):
+        return self.points[self._rows(i)]
+
+
+class SceneTester(SceneCrops):
+    """`SceneTester(scenes, colors=colors, num_classes=21, num_point=8192, num_buffer=1024, batch_size=4, split='test',
+    validation_size=500, label_values=np.arange(21), ignored_labels=(0,), with_rgb=True, rng=np.random)`.
+
+    scenes: a list of (n_i,3) float32 sub-sampled scenes (numpy arrays or device tensors) in the order of the reference's
+    input_trees[split]; colors: their (n_i,3) float32 colour rows (with_rgb).  The model sees C = num_classes logits and the
+    tables hold C - 1 classes (T:95, 108); label_values lists every label, ignored ones included, so
+    C - 1 + len(ignored_labels) == len(label_values).  Construction draws `rng.rand(n_i) * 1e-3` scene after scene
+    (D:472-478); every crop then draws `rng.normal(scale=0.35, size=(1, 3))`, `rng.randint(0, num_buffer // 4)` and
+    `rng.shuffle` of its k indices.  abs_coords: append the reference's three extra feature columns float32(xyz + pick)
+    (D:539) to the model input."""
+
+    def __init__(self, scenes, colors=None, num_classes=21, num_point=8192, num_buffer=1024, batch_size=4, split="test",
+                 validation_size=500, label_values=None, ignored_labels=(0,), with_rgb=True, rng=np.random, in_radius=0.0,
+                 abs_coords=False, test_smooth=None):
+        if in_radius > 0:
+            raise NotImplementedError("SceneTester covers the k form only (in_radius == 0): the radius form's shuffle length is "
+                                      "known on the device alone")
+        if split not in SMOOTH:
+            raise ValueError('split must be "test" or "validation"')
+        _hip.require_device()
+        self.C, self.split, self.validation_size = int(num_classes), split, int(validation_size)
+        self.test_smooth = SMOOTH[split] if test_smooth is None else float(test_smooth)
+        self.label_values = np.arange(self.C, dtype=np.int32) if label_values is None else np.asarray(label_values, np.int32).reshape(-1)
+        self.ignored_labels = tuple(int(v) for v in ignored_labels)
+        self.ignored_mask = np.isin(self.label_values, self.ignored_labels).astype(np.int32)
+        self.L, self.nc = int(self.label_values.size), self.C - 1
+        if len(set(self.label_values.tolist())) != self.L:
+            raise ValueError("label_values must be distinct")
+        if self.nc < 1 or self.nc + int(self.ignored_mask.sum()) != self.L:
+            raise ValueError(f"num_classes - 1 = {self.nc} table columns + {int(self.ignored_mask.sum())} ignored labels != "
+                             f"{self.L} label values")
+        self._init_crops(scenes, colors, num_point, num_buffer, batch_size, validation_size, with_rgb, rng, abs_coords)
+        self.probs = torch.zeros((self.N, self.nc), dtype=torch.float32, device=self.device)
+        self.smooth_old = float(np.float32(self.test_smooth))      # numpy: python_float * float32_array -> float32 product
+        self.smooth_new = float(np.float32(1 - self.test_smooth))
+        self.labels_dev = torch.from_numpy(self.label_values).to(self.device)
+        self.ignored_dev = torch.from_numpy(self.ignored_mask).to(self.device)
+        self.checkpoints = []  # (epoch, new_min) of every checkpoint run() fired
+
     def vote(self, logits, point_inds, cloud_inds, is_logits=True):
         """T:141-149 / 283-291 for one batch, crop after crop: logits (B,num_point,C) f32 -- the table takes
         softmax(logits[..., 1:]) -- or, is_logits=False, probabilities (B,num_point,C-1)."""
@@ -217,21 +243,9 @@ class SceneTester:
         return epochs
 
     # ---- state
-    def _rows(self, i):
-        return slice(int(self.offsets_host[i]), int(self.offsets_host[i + 1]))
-
     def test_probs(self, i):
         """scene i's float32 vote table (n_i, C-1), a device view"""
         return self.probs[self._rows(i)]
-
-    def potentials_of(self, i):
-        return self.potentials[self._rows(i)]
-
-    def min_potentials(self):
-        return self.min_pots.cpu().numpy()
-
-    def scene_points(self, i):
-        return self.points[self._rows(i)]
 
     # ---- reprojection and scoring
     def proj_inds(self, i, raw_points):
