@@ -760,6 +760,50 @@ int pasnl_scan_augment(int b, int num_point, int width, const float* src, float*
                        int anisotropic, int sym_x, int sym_y, int sym_z, float noise, float color, unsigned long long seed,
                        const unsigned long long* item0, float* out_params, float* out_noise, pasnl_stream_t stream);
 
+/* ---- The radius form of the grid crops, `in_radius > 0` (csrc/radius_crop.hip): ScanNet/scannet_dataset_grid.py (D) :491-492
+ * and SemanticKITTI/semantic_kitti_dataset_grid.py (K) :268-269, `query_radius(centre, r=in_radius)[0]` on the scan's sklearn
+ * KDTree, and the lines that make a crop of the member list (D:500-501, 519-539, 692-703; K:274-283).  The crop shuffles
+ * POSITIONS of that list and its length is the count, so the count goes to the host (one read-back per crop) between the two
+ * entries. */
+
+/* The per-chunk counts of the two members entries below: one int per chunk of 64 positions of the largest scan, per crop. */
+size_t pasnl_scan_radius_workspace_bytes(int b, long nmax);
+
+/* The member lists of b crops (K:268-269): crop c reads its scan and float32 centre from desc[c]; a point is a member when
+ * ((dx*dx)+(dy*dy))+(dz*dz) <= radius*radius in DOUBLE with dx = (double)x - (double)cx -- the rule of pasnl_knn_crop's radius
+ * form, sklearn's on its float64 copy; a NaN coordinate is no member.  order: a flat (N,) i32 array beside the flat points,
+ * order[offset + p] the in-scan index of tree position p (np.asarray(tree.idx_array) of the reference's tree; NULL: the
+ * identity); an entry outside [0, n) is skipped.  -> out_members[c*member_stride + j], j < out_count[c]: the members in
+ * POSITION order (sklearn's order of query_radius), entries behind the count not written; out_count (b) i32 exact.
+ * member_stride >= nmax (nothing is truncated), nmax: the largest scan's count (blocks past a crop's own count exit);
+ * radius > 0 and not NaN, else PASNL_EINVAL.  Ballots and an exclusive scan over chunks of 64 positions, no atomics: three
+ * launches, deterministic.  workspace: pasnl_scan_radius_workspace_bytes(b, nmax) bytes. */
+int pasnl_scan_radius_members(int b, long nmax, const float* points, const pasnl_scan_crop_t* desc, double radius, const int* order,
+                              int* out_members, long member_stride, int* out_count, void* workspace, size_t workspace_bytes,
+                              pasnl_stream_t stream);
+
+/* pasnl_scan_radius_members around the float64 centres of desc[0..b) (D:491-492: `query_radius(pick_point, r=in_radius)`): the
+ * same kernels behind a template parameter, dx = (double)x - cx. */
+int pasnl_scene_radius_members(int b, long nmax, const float* points, const pasnl_scene_crop_t* desc, double radius,
+                               const int* order, int* out_members, long member_stride, int* out_count, void* workspace,
+                               size_t workspace_bytes, pasnl_stream_t stream);
+
+/* The rest of crop_pc (K:274-283) for b crops: out_select[c][j] = members[c*member_stride + perm[c][j]] for j < num_point and
+ * out_points[c][j] = points[offset + out_select[c][j]], as pasnl_crop_order_permute writes them.  perm (b,num_point) i32: the
+ * host's composition of `shuffle_idx`, `[:num_point]` and the duplicated rows (K:277-281).  count (b) i32 is read on the
+ * device (the output of the members entry): a perm entry outside [0, count[c]) leaves its row and its select entry
+ * unwritten, and nothing behind the count is read.  One launch. */
+int pasnl_scan_radius_gather(int b, const pasnl_scan_crop_t* desc, const float* points, const int* members, long member_stride,
+                             const int* count, const int* perm, int num_point, int* out_select, float* out_points,
+                             pasnl_stream_t stream);
+
+/* The rest of the ScanNet crop (D:500-501, 519-539 with data_rep, D:692-703): the select rule of pasnl_scan_radius_gather, and
+ * the model input rows out_input (b,num_point,W) f32 under pasnl_scene_order_gather's contract -- xyz relative to the float64
+ * centre, the colour row (nfeat = 0: none, colors may be NULL), abs_coords. */
+int pasnl_scene_radius_gather(int b, const pasnl_scene_crop_t* desc, const float* points, const float* colors, int nfeat,
+                              const int* members, long member_stride, const int* count, const int* perm, int num_point,
+                              int abs_coords, int* out_select, float* out_input, pasnl_stream_t stream);
+
 /* ---- The ScanNet sliding-window whole-scene test loop on the device (ScanNet/scannet_dataset.py (D) :183-300
  * `ScannetDatasetWholeSceneSlidingWindow.__getitem__`, ScanNet/test_scannet.py (T) :96-103 `add_vote` and :107-196
  * `eval_one_epoch`).  One scene at a time: xyz (n,3) f32 is the scene's OWN buffer, moved in place vote after vote as the

@@ -12,8 +12,8 @@ synchronisation, capturable.  The RNG draws of the flow -- the potentials' init,
 RandomState in the reference's order, and the crop sequence is the reference's, crop for crop (tests/scene_flow_ref.py
 restates the flow in numpy; tests/test_scene_tester_flow.py pins it to the reference's generator).
 
-Only the k form (in_radius == 0, the reference default) is covered, and every scene must hold at least
-num_point + num_buffer + num_buffer // 4 - 1 points (9 471 at the defaults): a smaller scene would change k and pull
+Only the k form (in_radius == 0, the reference default) is covered here (the radius form: scene_radius.py), and every scene
+must hold at least num_point + num_buffer + num_buffer // 4 - 1 points (9 471 at the defaults): a smaller scene would change k and pull
 data_rep's np.random.choice into a stream whose length depends on the device-chosen scene.  Whether real ScanNet scenes at
 the reference's sub-sampling always clear that count has not been measured.
 
@@ -44,16 +44,17 @@ class SceneCrops:
     potentials, the host's draws of a batch and the device chain of its crops.  `SceneTester` adds the votes of the test and
     validation splits, `scene_trainer.SceneTrainer` the labels, weights and augmentation of the training split."""
 
-    def _init_crops(self, scenes, colors, num_point, num_buffer, batch_size, steps, with_rgb, rng, abs_coords):
+    def _init_crops(self, scenes, colors, num_point, num_buffer, batch_size, steps, with_rgb, rng, abs_coords, k_form=True):
+        """k_form: the checks and buffers of the k form (scene_radius skips them)"""
         self.S, self.B = len(scenes), int(batch_size)
         self.num_point, self.num_buffer, self.rng = int(num_point), int(num_buffer), rng
         self.abs_coords = bool(abs_coords)
         if self.S < 1 or self.B < 1 or int(steps) < 1:
             raise ValueError("at least one scene, one crop per batch and one batch per epoch")
-        if self.num_buffer // 4 < 1:
+        if k_form and self.num_buffer // 4 < 1:
             raise ValueError("num_buffer // 4 must be >= 1 (the crop draws randint(0, num_buffer // 4))")
         self.kcap = self.num_point + self.num_buffer + self.num_buffer // 4 - 1
-        if self.kcap > ORDER_CAP:
+        if k_form and self.kcap > ORDER_CAP:
             raise _hip.PasnlUnsupported(f"num_point + num_buffer + num_buffer//4 - 1 = {self.kcap} > {ORDER_CAP} (the LDS sort of "
                                         "pasnl_scene_order_gather)")
         dev = []
@@ -64,7 +65,7 @@ class SceneCrops:
             dev.append(t)
         self.sizes = [int(t.shape[0]) for t in dev]
         for i, n in enumerate(self.sizes):
-            if n < self.kcap:
+            if k_form and n < self.kcap:
                 raise ValueError(f"scene {i} has {n} points < num_point + num_buffer + num_buffer//4 - 1 = {self.kcap}: k would "
                                  "shrink and data_rep's np.random.choice would enter the RNG stream (D:495-496, 533-535)")
         self.F = 3 if with_rgb else 0
@@ -91,13 +92,14 @@ class SceneCrops:
         self.win = torch.empty((self.nmax,), dtype=torch.int32, device=self.device)
         _hip.launch("pasnl_scan_scratch_init", type(self).__name__, ctypes.c_long(self.nmax), _p(self.win))
         self.desc = torch.zeros((self.B, DESC_BYTES), dtype=torch.uint8, device=self.device)
-        self.idx = torch.empty((self.kcap,), dtype=torch.int32, device=self.device)
-        self.d2 = torch.empty((self.kcap,), dtype=torch.float64, device=self.device)
-        self.cnt = torch.empty((1,), dtype=torch.int32, device=self.device)
-        nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(1, ctypes.c_long(self.nmax)))
-        self.ws, self.ws_bytes = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device), nbytes
+        if k_form:
+            self.idx = torch.empty((self.kcap,), dtype=torch.int32, device=self.device)
+            self.d2 = torch.empty((self.kcap,), dtype=torch.float64, device=self.device)
+            self.cnt = torch.empty((1,), dtype=torch.int32, device=self.device)
+            nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(1, ctypes.c_long(self.nmax)))
+            self.ws, self.ws_bytes = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device), nbytes
         self.noise_stage = torch.empty((self.B, 3), dtype=torch.float64, device=self.device)
-        self.k_stage = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        self.k_stage = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
         self.perm_stage = torch.empty((self.B, self.num_point), dtype=torch.int32, device=self.device)
 
     # ---- one batch
@@ -180,8 +182,13 @@ class SceneTester(SceneCrops):
                  validation_size=500, label_values=None, ignored_labels=(0,), with_rgb=True, rng=np.random, in_radius=0.0,
                  abs_coords=False, test_smooth=None):
         if in_radius > 0:
-            raise NotImplementedError("SceneTester covers the k form only (in_radius == 0): the radius form's shuffle length is "
-                                      "known on the device alone")
+            raise NotImplementedError("SceneTester covers the k form only (in_radius == 0): the radius form is "
+                                      "pointasnl_amd.ScanNet.scene_radius.RadiusSceneTester")
+        self._init_tester(scenes, colors, num_classes, num_point, num_buffer, batch_size, split, validation_size, label_values,
+                          ignored_labels, with_rgb, rng, abs_coords, test_smooth)
+
+    def _init_tester(self, scenes, colors, num_classes, num_point, num_buffer, batch_size, split, validation_size, label_values,
+                     ignored_labels, with_rgb, rng, abs_coords, test_smooth, k_form=True):
         if split not in SMOOTH:
             raise ValueError('split must be "test" or "validation"')
         _hip.require_device()
@@ -196,7 +203,7 @@ class SceneTester(SceneCrops):
         if self.nc < 1 or self.nc + int(self.ignored_mask.sum()) != self.L:
             raise ValueError(f"num_classes - 1 = {self.nc} table columns + {int(self.ignored_mask.sum())} ignored labels != "
                              f"{self.L} label values")
-        self._init_crops(scenes, colors, num_point, num_buffer, batch_size, validation_size, with_rgb, rng, abs_coords)
+        self._init_crops(scenes, colors, num_point, num_buffer, batch_size, validation_size, with_rgb, rng, abs_coords, k_form)
         self.probs = torch.zeros((self.N, self.nc), dtype=torch.float32, device=self.device)
         self.smooth_old = float(np.float32(self.test_smooth))      # numpy: python_float * float32_array -> float32 product
         self.smooth_new = float(np.float32(1 - self.test_smooth))
@@ -218,6 +225,12 @@ class SceneTester(SceneCrops):
     def crops_per_epoch(self):
         return self.validation_size * self.B  # D:462-465
 
+    def _epoch(self, forward):
+        """one epoch of the generator: validation_size batches, each voted"""
+        for _ in range(self.validation_size):
+            inputs, inds, clouds = self.next_batch()
+            self.vote(forward(inputs), inds, clouds)
+
     def run(self, forward, num_votes=100, on_checkpoint=None, max_epochs=None):
         """The epoch loop of T:128-227 (test) / T:271-446 (validation): epochs of validation_size batches while
         last_min < num_votes; after each, new_min = min(min_potentials) is read back (the only synchronisation) and the
@@ -227,9 +240,7 @@ class SceneTester(SceneCrops):
         logits.  -> the number of epochs run; the checkpoints are appended to `self.checkpoints` as (epoch, new_min)."""
         epochs, last_min = 0, -0.5
         while last_min < num_votes:
-            for _ in range(self.validation_size):
-                inputs, inds, clouds = self.next_batch()
-                self.vote(forward(inputs), inds, clouds)
+            self._epoch(forward)
             new_min = float(self.min_pots.min().item())
             step = 2 if self.split == "test" else 1
             if last_min + step < new_min:

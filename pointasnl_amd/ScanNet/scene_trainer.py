@@ -16,8 +16,8 @@ order -- `rng.rand(n_i) * 1e-3` per scene at construction, then per crop `rng.no
 with no host synchronisation; the counters come down once per epoch.  The potentials persist across epochs, as the
 reference's do (reset_potentials runs when the generator is built, not when it is restarted).
 
-Only the k form (in_radius == 0) is covered and every scene must hold at least num_point + num_buffer + num_buffer // 4 - 1
-points, as for `SceneTester`.  There is no abs_coords option: `tf_map` keeps the colour columns only (D:562).
+Only the k form (in_radius == 0) is covered here (the radius form: scene_radius.RadiusSceneTrainer) and every scene must
+hold at least num_point + num_buffer + num_buffer // 4 - 1 points, as for `SceneTester`.  There is no abs_coords option: `tf_map` keeps the colour columns only (D:562).
 
 Deviations: the augmentation's generator is Philox4x32-10 (pointasnl_amd/grid_augment.py lays out every draw), not TF's, and
 the summation order of TF's matmul is not promised; the classify loss is pasnl_block_score's and is compared under a
@@ -46,8 +46,13 @@ class SceneTrainer(SceneCrops, GridTrainLoop):
                  label_values=None, label_weights=None, with_rgb=True, rng=np.random, seed=0, augment=True, in_radius=0.0,
                  augment_config=None):
         if in_radius > 0:
-            raise NotImplementedError("SceneTrainer covers the k form only (in_radius == 0): the radius form's shuffle length is "
-                                      "known on the device alone")
+            raise NotImplementedError("SceneTrainer covers the k form only (in_radius == 0): the radius form is "
+                                      "pointasnl_amd.ScanNet.scene_radius.RadiusSceneTrainer")
+        self._init_trainer(scenes, labels, colors, num_classes, num_point, num_buffer, batch_size, epoch_steps, label_values,
+                           label_weights, with_rgb, rng, seed, augment, augment_config)
+
+    def _init_trainer(self, scenes, labels, colors, num_classes, num_point, num_buffer, batch_size, epoch_steps, label_values,
+                      label_weights, with_rgb, rng, seed, augment, augment_config, k_form=True):
         _hip.require_device()
         self.C, self.epoch_steps = int(num_classes), int(epoch_steps)
         self.label_values = np.arange(self.C, dtype=np.int64) if label_values is None else np.asarray(label_values, np.int64).reshape(-1)
@@ -63,7 +68,7 @@ class SceneTrainer(SceneCrops, GridTrainLoop):
         idx = order[pos]
         if idx.size and int(idx.max()) >= min(w.size, self.C):
             raise IndexError(f"class index {int(idx.max())} is out of bounds for {w.size} label weights and {self.C} classes (D:531)")
-        self._init_crops(scenes, colors, num_point, num_buffer, batch_size, epoch_steps, with_rgb, rng, False)
+        self._init_crops(scenes, colors, num_point, num_buffer, batch_size, epoch_steps, with_rgb, rng, False, k_form)
         self.P = self.num_point
         self.labels = torch.from_numpy(idx.astype(np.int32)).to(self.device)
         self.label_weights = torch.from_numpy(w.astype(np.float32)).to(self.device)

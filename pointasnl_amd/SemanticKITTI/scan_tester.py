@@ -8,7 +8,8 @@ the current stream (csrc/scan_test.hip, csrc/crop.hip): no host synchronisation,
 flow -- the possibility init, crop_pc's `buffer` and its shuffle -- depend on lengths the host knows, so they are drawn on
 the host from the caller's numpy RandomState in the reference's order, and the crop sequence is the reference's, crop for
 crop (tests/scan_flow_ref.py restates the flow in numpy; tests/test_scan_tester_flow.py pins it to the reference's
-generator).  Only the k form of crop_pc (in_radius == 0, the reference default) is covered.
+generator).  Only the k form of crop_pc (in_radius == 0, the reference default) is covered here; the radius form is
+scan_radius.RadiusScanTester.
 
 Deviations: the crops are fed unaugmented (the reference maps tf_augment_input over the test crops with TF's RNG, which
 cannot be reproduced); the softmax of a vote is computed here in float32, not by TensorFlow (a vote may differ by one
@@ -39,18 +40,22 @@ class ScanTester:
     def __init__(self, scans, num_classes=20, num_point=10240, num_buffer=1024, batch_size=8, test_smooth=0.98, rng=np.random,
                  in_radius=0.0):
         if in_radius > 0:
-            raise NotImplementedError("ScanTester covers crop_pc's k form only (in_radius == 0): the radius form's shuffle length "
-                                      "is known on the device alone")
+            raise NotImplementedError("ScanTester covers crop_pc's k form only (in_radius == 0): the radius form is "
+                                      "pointasnl_amd.SemanticKITTI.scan_radius.RadiusScanTester")
+        self._init_scans(scans, num_classes, num_point, num_buffer, batch_size, test_smooth, rng)
+
+    def _init_scans(self, scans, num_classes, num_point, num_buffer, batch_size, test_smooth, rng, k_form=True):
+        """the scans, possibilities and votes; k_form: the checks and buffers of crop_pc's k form (scan_radius skips them)"""
         _hip.require_device()
         self.S, self.B, self.C = len(scans), int(batch_size), int(num_classes)
         self.num_point, self.num_buffer, self.test_smooth, self.rng = int(num_point), int(num_buffer), float(test_smooth), rng
         if self.S < self.B:
             raise ValueError(f"{self.S} scans < batch_size {self.B}: an epoch of int(S/B)*B*4 crops would be empty (the reference "
                              "would loop forever)")
-        if self.num_buffer // 4 < 1:
+        if k_form and self.num_buffer // 4 < 1:
             raise ValueError("num_buffer // 4 must be >= 1 (crop_pc draws randint(0, num_buffer // 4))")
         self.kcap = self.num_point + self.num_buffer + self.num_buffer // 4 - 1
-        if self.kcap > ORDER_CAP:
+        if k_form and self.kcap > ORDER_CAP:
             raise _hip.PasnlUnsupported(f"num_point + num_buffer + num_buffer//4 - 1 = {self.kcap} > {ORDER_CAP} (the LDS sort of "
                                         "pasnl_crop_order_permute)")
         dev = []
@@ -61,7 +66,7 @@ class ScanTester:
             dev.append(t)
         self.sizes = [int(t.shape[0]) for t in dev]
         for i, n in enumerate(self.sizes):
-            if n < self.kcap:
+            if k_form and n < self.kcap:
                 raise ValueError(f"scan {i} has {n} points < num_point + num_buffer + num_buffer//4 - 1 = {self.kcap} (sklearn's "
                                  "query would raise on k > n)")
         self.offsets_host = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
@@ -81,13 +86,14 @@ class ScanTester:
         _hip.launch("pasnl_scan_scratch_init", "ScanTester", ctypes.c_long(self.nmax), _p(self.win))
         self.scratch = torch.zeros((1,), dtype=torch.float32, device=self.device)
         self.desc = torch.zeros((self.B, DESC_BYTES), dtype=torch.uint8, device=self.device)
-        self.idx = torch.empty((self.kcap,), dtype=torch.int32, device=self.device)
-        self.d2 = torch.empty((self.kcap,), dtype=torch.float64, device=self.device)
-        self.cnt = torch.empty((1,), dtype=torch.int32, device=self.device)
-        nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(1, ctypes.c_long(self.nmax)))
-        self.ws, self.ws_bytes = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device), nbytes
-        self.k_stage = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        self.k_stage = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
         self.perm_stage = torch.empty((self.B, self.num_point), dtype=torch.int32, device=self.device)
+        if k_form:
+            self.idx = torch.empty((self.kcap,), dtype=torch.int32, device=self.device)
+            self.d2 = torch.empty((self.kcap,), dtype=torch.float64, device=self.device)
+            self.cnt = torch.empty((1,), dtype=torch.int32, device=self.device)
+            nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(1, ctypes.c_long(self.nmax)))
+            self.ws, self.ws_bytes = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device), nbytes
         self.smooth_old = int(np.array(self.test_smooth, dtype=np.float16).view(np.uint16))  # numpy: test_smooth * float16 -> f16
         self.smooth_new = float(np.float32(1 - self.test_smooth))                           # (1 - test_smooth) * float32 probs
 

@@ -16,7 +16,8 @@ reference's order, `rng.choice(n_i, 1)` (K:220), `rng.randint(0, num_buffer // 4
 then `step(points, labels, weights) -> (B,P,C) f32 logits` and pasnl_block_train_score (T:242-250).  symmetries=(True, False,
 False) is the training split; (False, False, False) gives the validation split's generator (K:198-202).
 
-Only crop_pc's k form (in_radius == 0) is covered; a scan smaller than k raises ValueError with sklearn's message, as
+Only crop_pc's k form (in_radius == 0) is covered here (the radius form: scan_radius.RadiusScanTrainer); a scan smaller
+than k raises ValueError with sklearn's message, as
 `DeviceScan.query` does.
 
 Deviations: scans are arrays in memory, not files; the augmentation's generator is Philox4x32-10
@@ -49,18 +50,25 @@ class ScanTrainer(GridTrainLoop):
     def __init__(self, scans, labels, num_classes=20, num_point=10240, num_buffer=1024, batch_size=4, label_weights=None,
                  symmetries=(True, False, False), rng=np.random, seed=0, augment=True, in_radius=0.0, augment_config=None):
         if in_radius > 0:
-            raise NotImplementedError("ScanTrainer covers crop_pc's k form only (in_radius == 0): the radius form's shuffle length "
-                                      "is known on the device alone")
+            raise NotImplementedError("ScanTrainer covers crop_pc's k form only (in_radius == 0): the radius form is "
+                                      "pointasnl_amd.SemanticKITTI.scan_radius.RadiusScanTrainer")
+        self._init_scans(scans, labels, num_classes, num_point, num_buffer, batch_size, label_weights, symmetries, rng, seed, augment,
+                         augment_config)
+
+    def _init_scans(self, scans, labels, num_classes, num_point, num_buffer, batch_size, label_weights, symmetries, rng, seed, augment,
+                    augment_config, k_form=True):
+        """the scans, labels, weights, augmentation and tallies; k_form: the checks and buffers of crop_pc's k form (scan_radius
+        skips them)"""
         _hip.require_device()
         self.S, self.B, self.C = len(scans), int(batch_size), int(num_classes)
         self.num_point, self.num_buffer, self.rng = int(num_point), int(num_buffer), rng
         self.P = self.num_point
         if self.S < 1 or self.B < 1:
             raise ValueError("at least one scan and one crop per batch")
-        if self.num_buffer // 4 < 1:
+        if k_form and self.num_buffer // 4 < 1:
             raise ValueError("num_buffer // 4 must be >= 1 (crop_pc draws randint(0, num_buffer // 4))")
         self.kcap = self.num_point + self.num_buffer + self.num_buffer // 4 - 1
-        if self.kcap > ORDER_CAP:
+        if k_form and self.kcap > ORDER_CAP:
             raise _hip.PasnlUnsupported(f"num_point + num_buffer + num_buffer//4 - 1 = {self.kcap} > {ORDER_CAP} (the LDS sort of "
                                         "pasnl_crop_order_permute)")
         dev = []
@@ -71,7 +79,7 @@ class ScanTrainer(GridTrainLoop):
             dev.append(t)
         self.sizes = [int(t.shape[0]) for t in dev]
         for n in self.sizes:
-            if n < self.kcap:  # sklearn/neighbors/_binary_tree.pxi, query(): any k the crop may draw must fit
+            if k_form and n < self.kcap:  # sklearn/neighbors/_binary_tree.pxi, query(): any k the crop may draw must fit
                 raise ValueError("k must be less than or equal to the number of training points")
         w = np.ones((self.C,), np.float32) if label_weights is None else np.asarray(label_weights).reshape(-1)
         host = flat_labels(labels, self.sizes, "scan")
@@ -87,13 +95,14 @@ class ScanTrainer(GridTrainLoop):
         self.label_weights = torch.from_numpy(w.astype(np.float32)).to(self.device)
         B = self.B
         self.desc = torch.zeros((B, DESC_BYTES), dtype=torch.uint8, device=self.device)
-        self.idx = torch.empty((B, self.kcap), dtype=torch.int32, device=self.device)
-        self.d2 = torch.empty((B, self.kcap), dtype=torch.float64, device=self.device)
-        self.cnt = torch.empty((B,), dtype=torch.int32, device=self.device)
-        nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(B, ctypes.c_long(self.nmax)))
-        self.ws, self.ws_bytes = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device), nbytes
+        if k_form:
+            self.idx = torch.empty((B, self.kcap), dtype=torch.int32, device=self.device)
+            self.d2 = torch.empty((B, self.kcap), dtype=torch.float64, device=self.device)
+            self.cnt = torch.empty((B,), dtype=torch.int32, device=self.device)
+            nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(B, ctypes.c_long(self.nmax)))
+            self.ws, self.ws_bytes = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device), nbytes
         self.pick_stage = torch.empty((B,), dtype=torch.int32, device=self.device)
-        self.k_stage = torch.empty((B,), dtype=torch.int32, device=self.device)
+        self.k_stage = torch.zeros((B,), dtype=torch.int32, device=self.device)
         self.cloud_stage = torch.empty((B,), dtype=torch.int32, device=self.device)
         self.perm_stage = torch.empty((B, self.num_point), dtype=torch.int32, device=self.device)
         self.next_item = 0  # position in the epoch's list (K:214-216)

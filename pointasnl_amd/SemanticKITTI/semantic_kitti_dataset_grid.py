@@ -6,8 +6,8 @@ The reference keeps one pickled sklearn `KDTree` per voxel-subsampled scan (get_
 (`query_radius`, :269).  `DeviceScan` stands where that tree stood: it holds the scan in HBM and answers the two calls
 with ONE exact selection (`pasnl_knn_crop`, csrc/crop.hip; no tree is built) -- same argument meaning, same return
 structure, the same SET of points (ranked by the float64 squared distance sklearn ranks by); a tie at the k-th distance
-goes to the lowest indices (and `query_radius` lists its points by ascending index, sklearn in its tree's order: crop_pc
-shuffles them at once).  `crop_pc` below is the reference's flow on top of it: shuffle, truncate, duplicate-pad with the
+goes to the lowest indices (and `query_radius` lists its points by ascending index, sklearn in its tree's order -- crop_pc
+shuffles positions of that list, so hand `DeviceScan` the tree's `idx_array` for the reference's radius crop).  `crop_pc` below is the reference's flow on top of it: shuffle, truncate, duplicate-pad with the
 caller's numpy RNG, on the host as there.  The test loop around it -- possibility init, pick, crop, possibility update,
 votes and reprojection (:192-245 and test_semantic_kitti_grid.py) -- runs on the device in scan_tester.ScanTester.
 Datasets and the tf.data plumbing are out of scope.
@@ -24,9 +24,12 @@ class DeviceScan:
     """One scan in HBM, queried like the reference's `search_tree` (an sklearn.neighbors.KDTree over the same points).
 
     `DeviceScan(points)`: points (n,3) float32, numpy (copied over PCIe once, like unpickling the tree) or a CUDA tensor
-    (e.g. the output rows of grid_subsampling on the device).  `.data` is the (n,3) array view crop_pc indexes."""
+    (e.g. the output rows of grid_subsampling on the device).  `.data` is the (n,3) array view crop_pc indexes.
+    tree_order: `np.asarray(tree.idx_array)` of the reference's tree over the same points, a permutation of arange(n); with
+    it `query_radius` lists its points in sklearn's order (pasnl_scan_radius_members), so `crop_pc(..., in_radius > 0)` is
+    the reference's crop.  None: ascending index, as before."""
 
-    def __init__(self, points):
+    def __init__(self, points, tree_order=None):
         _hip.require_device()
         if isinstance(points, torch.Tensor):
             self.dev = _hip.as_dev(points, torch.float32)
@@ -40,6 +43,11 @@ class DeviceScan:
         nbytes = int(_hip.lib().pasnl_knn_crop_workspace_bytes(1, ctypes.c_long(self.n)))
         self._ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.dev.device)
         self._ws_bytes = nbytes
+        self.order = None
+        if tree_order is not None:
+            from pointasnl_amd.radius_crop import flat_tree_orders
+
+            self.order = torch.from_numpy(flat_tree_orders([tree_order], [self.n])).to(self.dev.device)
 
     @property
     def data(self):
@@ -87,11 +95,30 @@ class DeviceScan:
         X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
         if X.shape[0] != 1:
             raise ValueError("DeviceScan.query_radius answers one centre per call (crop_pc's use, :269)")
+        out = np.empty((1,), dtype=object)
+        if self.order is not None:
+            out[0] = self._members_in_tree_order(X[0].astype(np.float32), float(r))
+            return out
         idx, _, cnt = self.select(X[0].astype(np.float32), radius=float(r))
         m = int(cnt.item())
-        out = np.empty((1,), dtype=object)
         out[0] = idx[:m].cpu().numpy().astype(np.int64)
         return out
+
+    def _members_in_tree_order(self, centre, r):
+        """the points within r of centre in the order of the tree's idx_array (sklearn's), int64"""
+        desc = np.zeros(1, np.dtype([("offset", "<i8"), ("cloud", "<i4"), ("pick", "<i4"), ("n", "<i4"), ("k", "<i4"),
+                                     ("c", "<f4", 3), ("pad", "<i4")]))  # pasnl_scan_crop_t
+        desc["n"], desc["c"] = self.n, centre
+        dev = self.dev.device
+        d = torch.from_numpy(desc.view(np.uint8)).to(dev)
+        members = torch.empty((self.n,), dtype=torch.int32, device=dev)
+        cnt = torch.empty((1,), dtype=torch.int32, device=dev)
+        nbytes = int(_hip.lib().pasnl_scan_radius_workspace_bytes(1, ctypes.c_long(self.n)))
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        _hip.launch("pasnl_scan_radius_members", "query_radius", 1, ctypes.c_long(self.n), _hip.ptr(self.dev), _hip.ptr(d),
+                    ctypes.c_double(r), _hip.ptr(self.order), _hip.ptr(members), ctypes.c_long(self.n), _hip.ptr(cnt), _hip.ptr(ws),
+                    ctypes.c_size_t(nbytes))
+        return members[:int(cnt.item())].cpu().numpy().astype(np.int64)
 
 
 def select_batch(points, centres, k=None, kcap=None, radius=0.0, want_d2=False, workspace=None):

@@ -144,10 +144,9 @@ static __global__ __launch_bounds__(64 * COL_WAVES) void column_count_kernel(lon
   }
 }
 
-// pass 2
-static __global__ __launch_bounds__(256) void window_scan_kernel(long nchunks, int* __restrict__ hist, int* __restrict__ counts) {
-  __shared__ int wsum[4];
-  int* row = hist + (size_t)blockIdx.x * nchunks;
+// pass 2 for one row of per-chunk counts, by one workgroup of 256: an exclusive scan in place -> the row's total (every
+// thread's).  wsum: 4 ints of LDS.
+__device__ __forceinline__ int chunk_scan_exclusive(int* __restrict__ row, long nchunks, int* wsum) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int carry = 0;
   for (long base = 0; base < nchunks; base += 256) {
@@ -169,7 +168,13 @@ static __global__ __launch_bounds__(256) void window_scan_kernel(long nchunks, i
     carry += all;
     __syncthreads();
   }
-  if (threadIdx.x == 0) counts[blockIdx.x] = carry;
+  return carry;
+}
+
+static __global__ __launch_bounds__(256) void window_scan_kernel(long nchunks, int* __restrict__ hist, int* __restrict__ counts) {
+  __shared__ int wsum[4];
+  const int total = chunk_scan_exclusive(hist + (size_t)blockIdx.x * nchunks, nchunks, wsum);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 // pass 3: ascending index within every column.  out_mask may be null: then no mask is written.

@@ -65,7 +65,11 @@ class GridTrainLoop(BlockTrainLoop):
         for _ in range(self.steps_per_epoch):
             x, y, w, _, _ = self.next_batch()
             self.score(step(x, y, w), y, w)
-        self.num_batches = self.steps_per_epoch
+        return self._end_epoch(self.steps_per_epoch)
+
+    def _end_epoch(self, num_batches):
+        """the epoch's results after `num_batches` scored batches -> total_correct / float(total_seen)"""
+        self.num_batches = num_batches
         c = self.counters.cpu().numpy()  # the epoch's one readback
         self._final = dict(total_correct=int(c[0]), total_seen=int(c[1]), total_iou_deno=int(c[2]),
                            loss_sum=float(self.loss.cpu().numpy()[0]))

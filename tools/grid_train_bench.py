@@ -16,6 +16,10 @@ Prints one JSON line: crops per second of both, for both datasets (medians over 
                                    [--warmup 1] [--repeats 3] [--device-epochs 5]
 
 One timed device sample is --device-epochs epochs in a row.
+
+--in-radius R (R > 0): the radius form instead -- RadiusSceneTrainer / RadiusScanTrainer against the host chain (sklearn
+query_radius + numpy) and against SceneTrainer / ScanTrainer at the same num_point, unaugmented (tools/radius_bench.py);
+--kitti-in-radius is the SemanticKITTI radius (default: 5 R).
 """
 import argparse
 import json
@@ -35,6 +39,28 @@ def median(xs):
     return float(np.median(np.asarray(xs)))
 
 
+def radius_form(args):
+    import block_flow_ref as F
+    import radius_bench  # (tools/ is the script's directory)
+    from kitti_window_test_bench import lidar_scan
+
+    torch.cuda.set_device(0)
+    S, B = args.scenes, 4
+
+    def labels_of(k, n, c):
+        return np.random.default_rng(5 + k).integers(0, c, n).astype(np.int32)
+
+    pc = [F.scene(5 + k, args.points) for k in range(S)]
+    out = dict(metric="grid_train_loops_radius")
+    out["scannet"] = radius_bench.run("scene", "training", [p for p, _ in pc], [c for _, c in pc],
+                                      [labels_of(k, args.points, 21) for k in range(S)], args.in_radius, 8192, B, args.steps, 0,
+                                      args.warmup, args.repeats, 21)
+    scans = [lidar_scan(5 + k, args.kitti_points, args.radius) for k in range(S)]
+    out["kitti"] = radius_bench.run("scan", "training", scans, None, [labels_of(k, args.kitti_points, 20) for k in range(S)],
+                                    args.kitti_in_radius or 5 * args.in_radius, 10240, B, 0, 0, args.warmup, args.repeats, 20)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=150000)
@@ -45,7 +71,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--device-epochs", type=int, default=5)
+    ap.add_argument("--in-radius", type=float, default=0.0)
+    ap.add_argument("--kitti-in-radius", type=float, default=0.0)
     args = ap.parse_args()
+    if args.in_radius > 0:
+        return radius_form(args)
 
     from sklearn.neighbors import KDTree
 

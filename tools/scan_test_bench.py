@@ -9,6 +9,9 @@ Prints one JSON line: crops/s of both, their ratio, the device chain's us per cr
 and the reprojection's us per 120k-point raw scan.
 
   python tools/scan_test_bench.py [--scans 8] [--points 100000] [--batches 6] [--warmup 2] [--batch 8] [--num-point 10240]
+
+--in-radius R (R > 0): the radius form instead -- RadiusScanTester against the host chain (sklearn query_radius + numpy) and
+against ScanTester at the same num_point, input side only (tools/radius_bench.py); medians of three timed blocks.
 """
 import argparse
 import json
@@ -41,7 +44,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--num-point", type=int, default=10240)
+    ap.add_argument("--in-radius", type=float, default=0.0)
     args = ap.parse_args()
+    if args.in_radius > 0:
+        import radius_bench  # (tools/ is the script's directory)
+
+        torch.cuda.set_device(0)
+        scans = [lidar(1000 + i, args.points + 997 * i) for i in range(args.scans)]
+        labels = [np.zeros(len(s), np.int32) for s in scans]
+        print(json.dumps(radius_bench.run("scan", "test", scans, None, labels, args.in_radius, args.num_point, args.batch, 0,
+                                          args.batches, args.warmup, 3, 20)))
+        return
 
     from pointasnl_amd.models import pointasnl_sem_seg_res
     from pointasnl_amd.SemanticKITTI import scan_tester as T

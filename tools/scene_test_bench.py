@@ -9,6 +9,9 @@ Prints one JSON line: crops/s of both (medians over --repeats timed blocks), the
 (HIP events around next_batch alone), its launches per crop, and the confusion kernel's time for a 1e5-point scene.
 
   python tools/scene_test_bench.py [--scenes 6] [--points 100000] [--batches 6] [--warmup 2] [--repeats 3]
+
+--in-radius R (R > 0): the radius form instead -- RadiusSceneTester against the host chain (sklearn query_radius + numpy) and
+against SceneTester at the same num_point, input side only (tools/radius_bench.py).
 """
 import argparse
 import json
@@ -51,7 +54,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--in-radius", type=float, default=0.0)
     args = ap.parse_args()
+    if args.in_radius > 0:
+        import radius_bench  # (tools/ is the script's directory)
+
+        torch.cuda.set_device(0)
+        pc = [indoor(2000 + i, args.points + 997 * i) for i in range(args.scenes)]
+        labels = [np.zeros(len(p), np.int32) for p, _ in pc]
+        print(json.dumps(radius_bench.run("scene", "test", [p for p, _ in pc], [c for _, c in pc], labels, args.in_radius, 8192,
+                                          args.batch, args.batches, args.batches, args.warmup, args.repeats, 21)))
+        return
 
     from sklearn.neighbors import KDTree
 
