@@ -421,6 +421,19 @@ int pasnl_narrow_project2(long rows0, int kdim0, int n0, const float* x0, const 
                           long rows1, int kdim1, int n1, const float* x1, const float* w1, const float* bias1, float* out1,
                           pasnl_stream_t stream);
 
+/* The non-local cell of a NARROW level, attended in input space (csrc/nl_input.hip): what pasnl_narrow_project2 followed by
+ * pasnl_nl_attention computes -- out (b,p,cb) = softmax(Q K^T / sqrt(cb)) V with [K | V] = feature . wkv + bkv and
+ * Q = new_point . wq + bq (pointasnl_util.py:186-212; BN folded by the caller, no activation) -- without forming K, V or Q.
+ * K and V are linear in the c input channels, so per query u = Wk Q (c numbers; Q . bk is constant over the keys and cancels
+ * in the softmax), w_j = softmax_j(u . feature_j / sqrt(cb)), and out = (sum_j w_j feature_j) Wv + bv.  Within the cells'
+ * 1e-5 of the fp64 restatement, not the bits of the cb-wide form; a pure function of its inputs (no atomics, fixed orders).
+ * feature (b,n,c), new_point (b,p,cz), wkv (c,2cb), bkv (2cb), wq (cz,cb), bq (cb).  1 <= c <= 8, 1 <= cz <= 16, cb in
+ * {32, 64, 128}, b <= 65535, out 16-byte aligned, else PASNL_EUNSUPPORTED; n < 1 is PASNL_EINVAL; b == 0 or p == 0 is a
+ * successful no-op.  Used by all three models' first levels (the name's prefix keeps it with the classifier's entries). */
+int pasnl_cls_nl_cell_input(int b, int p, int n, int c, int cz, int cb, const float* feature, const float* new_point,
+                            const float* wkv, const float* bkv, const float* wq, const float* bq, float* out,
+                            pasnl_stream_t stream);
+
 /* Deterministic backward of gather_point / group_point / three_interpolate: the gradient row of a source point is
  * the sum of its contributions in ascending order of the forward output element -- the order of the reference's
  * sequential CPU loop (tf_interpolate.cpp:131-153) -- so results are bit-reproducible (the reference's GPU kernels,

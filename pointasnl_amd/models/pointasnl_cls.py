@@ -44,6 +44,10 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     # kernel"; supposed, not traced: layer 2's search is forked inside the forward there and now waits behind layer3_1's tiles):
     # two launches unless asked for
     fuse3_1 = not adaptive_sample or pointasnl_util.SA_TAIL_GROUP_ALL == "always"
+    # the same for layer 1's non-local cell in input space: its kernel is 44 us shorter there too, the step 0.5 % LONGER (1.421 ->
+    # 1.429 ms in every one of three alternated runs; EXPERIMENTS.md, "The non-local cell of a narrow level"): the cb-wide kernels
+    # unless asked for
+    nl_input_space = not adaptive_sample or pointasnl_util.NL_INPUT_SPACE == "always"
 
     # Set abstraction layers.  Layer 2's search (FPS + kNN) reads layer 1's sampled coordinates only, so it is forked onto
     # a side stream the moment those are final and runs beside layer 1's MFMA / GEMM work (pointasnl_util.Forked)
@@ -54,6 +58,7 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     l1_xyz, l1_points = PointASNLSetAbstraction(l0_xyz, l0_points, npoint=512, nsample=32, mlp=[64, 64, 128],
                                                 is_training=is_training, bn_decay=bn_decay, weight_decay=weight_decay,
                                                 scope='layer1', as_neighbor=as_neighbor[0], search=search, xyz_concat=True,
+                                                nl_input_space=nl_input_space,
                                                 group_all=dict(mlp=[128, 256, 512], scope='layer3_1', pooled_out=net[:, 1024:]) if fuse3_1 else None,
                                                 after_sampling=None if search2 else lambda xyz1: search2.append(
                                                     Forked(lambda: sa_search(xyz1, None, 128, 64), lazy=lazy_fork)))

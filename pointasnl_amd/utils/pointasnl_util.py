@@ -464,13 +464,16 @@ AS_PAD_PROJECTION = True  # AdaptiveSampling, wide layers: [K | V | Q] projectio
 XYZ_CONCAT = True  # False = ignore xyz_concat requests (the group_all module concatenates itself)
 CENTRE0 = True  # as_neighbor == 0 layers: the fused cell reads its centres from its own tiles (pasnl_sa_cell, new_xyz = NULL)
 NL_NARROW_PROJECT = True  # False = conv_kv / conv_query of narrow inputs as two vendor GEMMs
+NL_INPUT_SPACE = True  # narrow levels (<= 8 input channels): the non-local cell attends on the input rows (pasnl_cls_nl_cell_input) where the
+                       # step measured faster -- not the classifier with adaptive sampling; "always": there too (0.5 % slower); False = A/B
 
 
 def PointNonLocalCell(feature, new_point, mlp, is_training, bn_decay, weight_decay, scope, bn=True, scaled=True,
-                      mode='dot', project=True):
+                      mode='dot', project=True, input_space=True):
     """Mirror of pointasnl_util.py:175-219.  Every one of the P sampled points (new_point (B,P,1,C)) attends to ALL N points
     of the level (feature (B,N,C)) through a mlp[0]-wide bottleneck, and is projected back to mlp[-1] channels
-    -> (B,P,1,mlp[-1]).  project=False stops before the projection (the caller fuses it)."""
+    -> (B,P,1,mlp[-1]).  project=False stops before the projection (the caller fuses it); input_space=False keeps a narrow
+    level on the cb-wide kernels (a model's own default, see NL_INPUT_SPACE)."""
     if mode != 'dot' or not scaled:
         raise NotImplementedError("only mode='dot', scaled=True is reachable in the reference models (SURVEY a11)")
     with tf_util.variable_scope(scope):
@@ -487,13 +490,26 @@ def PointNonLocalCell(feature, new_point, mlp, is_training, bn_decay, weight_dec
                 wq, bq = st.layer(channel, bottleneck_channel, bn, weight_decay)
             n_all = feature.shape[1]
             feature, new_point = feature.contiguous(), new_point.contiguous()
-            kv = torch.empty((batch_size, n_all, 2 * bottleneck_channel), dtype=torch.float32, device=feature.device)
-            q = torch.empty((batch_size, npoint * nsample, bottleneck_channel), dtype=torch.float32, device=feature.device)
-            _hip.launch("pasnl_narrow_project2", "narrow_project", ctypes.c_long(batch_size * n_all), int(feature.shape[-1]),
-                        2 * bottleneck_channel, _hip.ptr(feature), _hip.ptr(wkv), _hip.ptr(bkv), _hip.ptr(kv),
-                        ctypes.c_long(batch_size * npoint * nsample), int(channel), bottleneck_channel, _hip.ptr(new_point), _hip.ptr(wq),
-                        _hip.ptr(bq), _hip.ptr(q))
-            new_nonlocal_point = nl_attention(q, kv)
+            new_nonlocal_point = None
+            if NL_INPUT_SPACE and input_space and feature.shape[-1] <= 8:
+                # keys and values are linear in <= 8 input channels: scores and the weighted sum are taken on the input rows
+                # themselves and go through Wv once per query (pasnl_cls_nl_cell_input) -- no kv, no q, no matrix kernel
+                att = torch.empty((batch_size, npoint * nsample, bottleneck_channel), dtype=torch.float32, device=feature.device)
+                try:
+                    _hip.launch("pasnl_cls_nl_cell_input", "nl_cell_input", batch_size, npoint * nsample, int(n_all),
+                                int(feature.shape[-1]), int(channel), bottleneck_channel, _hip.ptr(feature), _hip.ptr(new_point),
+                                _hip.ptr(wkv), _hip.ptr(bkv), _hip.ptr(wq), _hip.ptr(bq), _hip.ptr(att))
+                    new_nonlocal_point = att
+                except _hip.PasnlUnsupported:
+                    pass
+            if new_nonlocal_point is None:
+                kv = torch.empty((batch_size, n_all, 2 * bottleneck_channel), dtype=torch.float32, device=feature.device)
+                q = torch.empty((batch_size, npoint * nsample, bottleneck_channel), dtype=torch.float32, device=feature.device)
+                _hip.launch("pasnl_narrow_project2", "narrow_project", ctypes.c_long(batch_size * n_all), int(feature.shape[-1]),
+                            2 * bottleneck_channel, _hip.ptr(feature), _hip.ptr(wkv), _hip.ptr(bkv), _hip.ptr(kv),
+                            ctypes.c_long(batch_size * npoint * nsample), int(channel), bottleneck_channel, _hip.ptr(new_point),
+                            _hip.ptr(wq), _hip.ptr(bq), _hip.ptr(q))
+                new_nonlocal_point = nl_attention(q, kv)
             if not project:
                 return new_nonlocal_point
             new_nonlocal_point = tf_util.conv2d(
@@ -742,7 +758,8 @@ def _tail_packed(st, w):
 
 def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_decay, weight_decay, scope, bn=True,
                             use_knn=True, radius=None, as_neighbor=8, NL=True, search=None, after_sampling=None,
-                            xyz_concat=False, after_cell=None, before_after_conv=None, residual=None, group_all=None):
+                            xyz_concat=False, after_cell=None, before_after_conv=None, residual=None, group_all=None,
+                            nl_input_space=True):
     '''Mirror of pointasnl_util.py:221-292: one PointASNL set-abstraction layer.
         xyz (B,N,3), feature (B,N,C)  ->  new_xyz (B,npoint,3), new_points (B,npoint,mlp[-1])
     npoint points are sampled (FPS) and moved by AdaptiveSampling over their first `as_neighbor` neighbours; each keeps
@@ -863,7 +880,7 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
             att = None
             if NL:
                 att = PointNonLocalCell(feature, new_feature.unsqueeze(1), [cb, nl_channel], is_training, bn_decay,
-                                        weight_decay, scope, bn, project=False)  # (B, P, cb)
+                                        weight_decay, scope, bn, project=False, input_space=nl_input_space)  # (B, P, cb)
             if before_after_conv is not None:
                 before_after_conv()
             after = tf_util.conv2d(new_point, c_out, [1, new_point.shape[2]], padding='VALID', stride=[1, 1], bn=bn,
@@ -936,7 +953,7 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         if NL:
             new_nonlocal_point = PointNonLocalCell(feature, new_feature.unsqueeze(1),
                                                    [max(32, num_channel // 2), nl_channel], is_training, bn_decay,
-                                                   weight_decay, scope, bn)
+                                                   weight_decay, scope, bn, input_space=nl_input_space)
 
         # ---- skip connection (:257-261)
         skip_spatial = tf_util.conv1d(skip_spatial, mlp[-1], 1, padding='VALID', stride=1, bn=bn,
