@@ -245,13 +245,48 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn_kernel(int n, int m, in
 // More than 128 candidates (heavy ties / duplicates) falls back to the insertion kernel's method in a third
 // pass, so the result is exact for every input.  Distances are compared as their bit patterns (non-negative
 // floats order like unsigned ints).
+// Clouds of at most 1024 points (NIT = 8 or 16 iterations of 64 points) run the RESIDENT form: pass 1 keeps
+// every distance it computes in registers (NIT x QW VGPRs), so pass 2 reads no LDS and does no arithmetic --
+// one v_cmp per kept distance gives a lane mask, scalar popcounts give the exact candidate count, and only
+// a query that fits the buffer writes its candidates (mbcnt offset, no capacity test).  Larger clouds stream
+// the cloud twice as described above (NIT = 0).
 // ---------------------------------------------------------------------------------------------
 constexpr int KNN2_CAP = 128;  // candidate buffer per query (keys)
+constexpr int KNN2_BLOCK = 4;  // resident form: iterations (of 64 points) per block; a block past the cloud's end is skipped
 
-template <int R, int QW, typename IdxT>
+// Resident pass 1, one block: the distances of points [g*256, g*256 + 256) to the wave's QW queries, kept as bits in dr (a
+// point past the cloud's end as 0xffffffff: above every bound U, and min / max below leave m1, m2 what INF_BITS would), and
+// folded into the lane minima.  TAIL = false: the whole block lies inside the cloud, no select.
+template <int R, int QW, bool TAIL>
+__device__ __forceinline__ void knn2_resident_block(int g, int n, int lane, const float* sx, const float* sy, const float* sz,
+                                                    const float (&qx)[QW], const float (&qy)[QW], const float (&qz)[QW],
+                                                    uint32_t (*dr)[QW], uint32_t (&m1)[QW], uint32_t (&m2)[QW]) {
+#pragma unroll
+  for (int e = 0; e < KNN2_BLOCK; ++e) {
+    const int it = g * KNN2_BLOCK + e;
+    const int p = it * 64 + lane;
+    const float x = sx[p], y = sy[p], z = sz[p];  // p < 1024 <= SEARCH_TILE; stale words past n are masked below
+    float dq[QW];
+    dist2_multi<QW>(qx, qy, qz, x, y, z, dq);
+#pragma unroll
+    for (int q = 0; q < QW; ++q) {
+      uint32_t di = __float_as_uint(dq[q]);
+      if (TAIL) di = p < n ? di : 0xffffffffu;
+      dr[it][q] = di;
+      if (R == 2) m2[q] = min(m2[q], max(m1[q], di));
+      m1[q] = min(m1[q], di);
+    }
+  }
+}
+
+// NIT = 0: any n, the cloud streams through LDS once per pass and pass 2 computes the distances again.
+// NIT = 8, 16 (the resident form, n <= 64 * NIT <= 1024): pass 1 keeps every distance in registers, pass 2 reads them.
+template <int R, int QW, typename IdxT, int NIT = 0>
 __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, int k, const float* __restrict__ support,
                                                                 const float* __restrict__ queries, IdxT* __restrict__ idx,
                                                                 float* __restrict__ dist_out, const KnnTieFlags flags) {
+  static_assert(NIT % KNN2_BLOCK == 0 && NIT * 64 + 128 <= SEARCH_TILE,
+                "the resident form is one LDS tile, walked in whole blocks, with 128 words behind the cloud to spare (pass 2)");
   __shared__ float sx[SEARCH_TILE], sy[SEARCH_TILE], sz[SEARCH_TILE];
   __shared__ unsigned long long cand[SEARCH_WAVES * QW][KNN2_CAP];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -269,8 +304,26 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
     qx[q] = p[0]; qy[q] = p[1]; qz[q] = p[2];
     m1[q] = INF_BITS; m2[q] = INF_BITS;
   }
+  uint32_t dr[NIT > 0 ? NIT : 1][QW];  // resident form: the distance bits of point it*64 + lane to query q
   // ---- pass 1: per-lane R smallest distances
-  for (int base = 0; base < n; base += SEARCH_TILE) {
+  if constexpr (NIT > 0) {
+    stage_tile(cloud, n, 0, n, sx, sy, sz);
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < NIT / KNN2_BLOCK; ++g) {
+      if ((g + 1) * KNN2_BLOCK * 64 <= n) {  // (wave-uniform)
+        knn2_resident_block<R, QW, false>(g, n, lane, sx, sy, sz, qx, qy, qz, dr, m1, m2);
+      } else if (g * KNN2_BLOCK * 64 < n) {
+        knn2_resident_block<R, QW, true>(g, n, lane, sx, sy, sz, qx, qy, qz, dr, m1, m2);
+      } else {
+#pragma unroll
+        for (int e = 0; e < KNN2_BLOCK; ++e)
+#pragma unroll
+          for (int q = 0; q < QW; ++q) dr[g * KNN2_BLOCK + e][q] = 0xffffffffu;
+      }
+    }
+  }
+  for (int base = 0; NIT == 0 && base < n; base += SEARCH_TILE) {
     int tcnt = min(SEARCH_TILE, n - base);
     __syncthreads();
     stage_tile(cloud, n, base, tcnt, sx, sy, sz);
@@ -308,7 +361,39 @@ __global__ __launch_bounds__(SEARCH_WAVES * 64) void knn2_kernel(int n, int m, i
   int cnt[QW];
 #pragma unroll
   for (int q = 0; q < QW; ++q) cnt[q] = 0;
-  for (int base = 0; base < n; base += SEARCH_TILE) {
+  if constexpr (NIT > 0) {
+    // resident: one compare per kept distance gives the iteration's lane mask; the exact total first (scalar popcounts), so
+    // that an overflowing query keeps nothing and the others need no capacity test per candidate
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);  // in an SGPR: the candidate row's address is scalar arithmetic
+#pragma unroll
+    for (int q = 0; q < QW; ++q) {
+      unsigned long long hit[NIT];
+      int c = 0;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        hit[it] = __ballot(dr[it][q] <= U[q]);  // (a skipped block holds 0xffffffff: no bit)
+        c += (int)__builtin_popcountll(hit[it]);
+      }
+      cnt[q] = c;
+      const bool fits = c <= KNN2_CAP;  // (wave-uniform) else the fallback pass answers this query and nothing is kept
+      // Straight-line stores: a candidate goes to its slot, every other lane to a sink of its own -- the 128 words of sx behind
+      // point 64 * NIT, which such a cloud never stages -- so no store sits behind an exec mask and a skip branch.  A query
+      // that does not fit sends its candidates to the sink as well (rank < 64, and the slot pointer does not advance).
+      uint32_t* const sink0 = reinterpret_cast<uint32_t*>(sx) + NIT * 64;
+      uint32_t* const sink = sink0 + 2 * lane;
+      uint32_t* run = fits ? reinterpret_cast<uint32_t*>(cand[wave_u * QW + q]) : sink0;  // (uniform) the next free slot
+      const int step = fits ? 2 : 0;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(hit[it] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit[it], 0u));
+        uint32_t* const dst = dr[it][q] <= U[q] ? run + 2 * rank : sink;
+        dst[0] = (uint32_t)(it * 64 + lane);  // the key (distance bits << 32 | index), low word first
+        dst[1] = dr[it][q];
+        run += step * (int)__builtin_popcountll(hit[it]);
+      }
+    }
+  }
+  for (int base = 0; NIT == 0 && base < n; base += SEARCH_TILE) {
     int tcnt = min(SEARCH_TILE, n - base);
     if (n > SEARCH_TILE) {  // single-tile clouds are still resident from pass 1
       __syncthreads();
@@ -824,8 +909,14 @@ int pasnl::knn_brute_launch(int b, int n, int m, int k, const float* support, co
     dim3 grid((m + SEARCH_WAVES * qw - 1) / (SEARCH_WAVES * qw), b), block(SEARCH_WAVES * 64);
     with_index_type(idx_is_i64, [&](auto tag) {
       using T = decltype(tag);
-      auto kern = k <= 32 ? (qw == 4 ? knn2_kernel<1, 4, T> : qw == 2 ? knn2_kernel<1, 2, T> : knn2_kernel<1, 1, T>)
-                          : (qw == 4 ? knn2_kernel<2, 4, T> : qw == 2 ? knn2_kernel<2, 2, T> : knn2_kernel<2, 1, T>);
+      // the resident form (every distance computed once and kept in registers) wherever the cloud is at most 16 iterations
+      auto pick = [&](auto nit) {
+        constexpr int NIT = decltype(nit)::value;
+        return k <= 32 ? (qw == 4 ? knn2_kernel<1, 4, T, NIT> : qw == 2 ? knn2_kernel<1, 2, T, NIT> : knn2_kernel<1, 1, T, NIT>)
+                       : (qw == 4 ? knn2_kernel<2, 4, T, NIT> : qw == 2 ? knn2_kernel<2, 2, T, NIT> : knn2_kernel<2, 1, T, NIT>);
+      };
+      auto kern = n <= 512 ? pick(std::integral_constant<int, 8>{})
+                           : n <= 1024 ? pick(std::integral_constant<int, 16>{}) : pick(std::integral_constant<int, 0>{});
       hipLaunchKernelGGL(kern, grid, block, 0, st, n, m, k, support, queries, static_cast<T*>(idx), dist2, flags);
     });
     return pasnl_launch_status();
