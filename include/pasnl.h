@@ -773,6 +773,41 @@ int pasnl_scan_augment(int b, int num_point, int width, const float* src, float*
                        int anisotropic, int sym_x, int sym_y, int sym_z, float noise, float color, unsigned long long seed,
                        const unsigned long long* item0, float* out_params, float* out_noise, pasnl_stream_t stream);
 
+/* ---- The per-epoch evaluation of the grid pipelines on the device (csrc/grid_eval.hip): `eval_one_epoch` of
+ * ScanNet/train_scannet_grid.py (S) :304-434 and SemanticKITTI/train_semantic_kitti_grid.py (K) :265-330.  The generators
+ * are the entries above; the float32 IoU arithmetic on the (nl,nl) matrix stays on the host (one read-back per epoch).  None
+ * of the three entries synchronises with the host.  `ignored`: nl ints in HOST memory (non-zero: the label is ignored),
+ * read by the call; they travel as a kernel argument.  nl <= 64, else PASNL_EUNSUPPORTED; nc + the number of ignored labels
+ * != nl -> PASNL_EINVAL. */
+
+/* The per-crop confusions of a whole batch, summed (S:359-368, K:301-310), ADDED to out (nl,nl) i64, rows the truth.
+ * is_logits: values (b,num_point,nc+1) f32 and probs = softmax(values[..., 1:]) in f32 (S:310, K:268), in the operation order
+ * of pasnl_scene_vote's softmax; otherwise values (b,num_point,nc) f32 are the probabilities.  The prediction is np.argmax of
+ * the float32 PROBABILITIES with a zero inserted at every ignored l (the first maximum, numpy's NaN rule: logits that round
+ * to equal probabilities give the first index); truth (b,num_point) i32 class indices, one outside [0, nl) is dropped.
+ * out[truth][prediction] += 1.  b <= 65535; b == 0 is a no-op.  ONE launch: rows staged through LDS in tiles of 256 at an odd
+ * row stride, counters in LDS, one flush per workgroup with 64-bit integer atomics. */
+int pasnl_scan_eval_confusion(int b, int num_point, int nc, const float* values, int is_logits, const int* truth, const int* ignored,
+                              int nl, long long* out, pasnl_stream_t stream);
+
+/* S:346-351 for b crops, crop after crop in batch order, into the FLOAT64 table val_probs ((N,nc) rows, scene c at row
+ * offsets[c]): new = smooth_old * old + (double)(smooth_new * probs) -- numpy >= 2's `val_smooth * float64_array +
+ * (1 - val_smooth) * float32_array`: a float64 product with smooth_old = val_smooth, a FLOAT32 product with smooth_new =
+ * float32(1 - val_smooth), widened and added in float64; nothing is contracted.  values, is_logits, select, cloud, win: as in
+ * pasnl_scene_vote (a repeated index within a crop: the last occurrence wins).  nc <= 64.  Two launches per crop. */
+int pasnl_scene_eval_vote(int b, int num_point, int nc, const float* values, int is_logits, const int* select, const int* cloud,
+                          const long long* offsets, double smooth_old, float smooth_new, double* val_probs, int* win,
+                          pasnl_stream_t stream);
+
+/* The voting evaluation of one scene (S:396-410): sub_preds[r] = np.argmax of row r of the scene's float64 table probs (n,nc)
+ * with a zero inserted at every ignored l (an index into label_values; once per sub-sampled point, into the caller's (n,)
+ * i32 buffer); then for the m evaluation points out[index of labels[j] in label_values][sub_preds[proj[j]]] += 1 into (nl,nl)
+ * i64.  proj == NULL: j.  A label that is not a listed value is dropped (sklearn); proj[j] outside [0, n) is ignored.  m == 0:
+ * sub_preds only; n == 0: a no-op.  Two launches. */
+int pasnl_scene_eval_vote_confusion(long n, const double* probs, int nc, long m, const int* proj, const int* labels,
+                                    const int* label_values, const int* ignored, int nl, int* sub_preds, long long* out,
+                                    pasnl_stream_t stream);
+
 /* ---- The radius form of the grid crops, `in_radius > 0` (csrc/radius_crop.hip): ScanNet/scannet_dataset_grid.py (D) :491-492
  * and SemanticKITTI/semantic_kitti_dataset_grid.py (K) :268-269, `query_radius(centre, r=in_radius)[0]` on the scan's sklearn
  * KDTree, and the lines that make a crop of the member list (D:500-501, 519-539, 692-703; K:274-283).  The crop shuffles

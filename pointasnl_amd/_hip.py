@@ -22,6 +22,7 @@ SYMBOLS = [
     "pasnl_nl_attention", "pasnl_nl_attention_workspace_bytes", "pasnl_nl_attention_ws", "pasnl_as_attention", "pasnl_as_reweight", "pasnl_sa_local_cell", "pasnl_sa_cell", "pasnl_sa_cell_centre0", "pasnl_sa_cell_packed", "pasnl_sa_project", "pasnl_sa_cell_pre", "pasnl_sa_cell_pre_centre0", "pasnl_sa_tail", "pasnl_sa_tail_cat", "pasnl_sa_tail_res", "pasnl_sa_tail_packed_weights_bytes", "pasnl_sa_tail_pack_weights", "pasnl_sa_tail_packed", "pasnl_decode_cell", "pasnl_decode_cell_tiled", "pasnl_decode_cell_tiled_v4", "pasnl_max_pool_rows", "pasnl_max_pool_rows_strided", "pasnl_mlp3_max_pool_workspace_bytes", "pasnl_mlp3_max_pool", "pasnl_mlp3_packed_weights_bytes", "pasnl_mlp3_pack_weights", "pasnl_dense_rows_workspace_bytes", "pasnl_dense_rows", "pasnl_dense_splitk_workspace_bytes", "pasnl_dense_splitk", "pasnl_bf16x3_weights_bytes", "pasnl_bf16x3_split_weights", "pasnl_dense_bf16x3", "pasnl_narrow_project2", "pasnl_take_neighbor0", "pasnl_as_gather", "pasnl_as_attention_qkv", "pasnl_as_attention_proj", "pasnl_as_cell_narrow", "pasnl_as_cell_wide", "pasnl_as_cell_wide_ld", "pasnl_as_reweight_x", "pasnl_grid_subsample_workspace_bytes", "pasnl_grid_subsample", "pasnl_knn_crop_workspace_bytes", "pasnl_knn_crop",
     "pasnl_scan_pick", "pasnl_knn_crop_indirect", "pasnl_crop_order_permute", "pasnl_scan_possibility_update", "pasnl_scan_scratch_init", "pasnl_scan_vote", "pasnl_scan_reproject_workspace_bytes", "pasnl_scan_reproject", "pasnl_scan_labels",
     "pasnl_scan_pick_given", "pasnl_scan_train_labels", "pasnl_scan_augment",
+    "pasnl_scan_eval_confusion", "pasnl_scene_eval_vote", "pasnl_scene_eval_vote_confusion",
     "pasnl_scan_radius_workspace_bytes", "pasnl_scan_radius_members", "pasnl_scene_radius_members", "pasnl_scan_radius_gather", "pasnl_scene_radius_gather",
     "pasnl_scene_pick", "pasnl_knn_crop_scene", "pasnl_scene_pick_crop", "pasnl_scene_order_gather", "pasnl_scene_potential_update", "pasnl_scene_vote", "pasnl_scene_labels", "pasnl_confusion_matrix",
     "pasnl_window_noise", "pasnl_window_bounds", "pasnl_window_hist_bytes", "pasnl_window_count", "pasnl_window_fill", "pasnl_window_gather", "pasnl_window_vote", "pasnl_window_pool_labels",

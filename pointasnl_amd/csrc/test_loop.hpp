@@ -90,12 +90,21 @@ static __global__ __launch_bounds__(256) void vote_mark_kernel(int num_point, co
   if (j < num_point) atomicMax(&win[select[j]], j);
 }
 
-// tf.nn.softmax of one row in float32: max, exp(x - max), their sum in index order, the division
+// tf.nn.softmax of one row in float32: max, exp(x - max), their sum in index order, the division.  The two pieces serve a
+// row that is read in passes (grid_eval.hip: from LDS, no private array): the same function on the same argument gives the
+// same bits, so a term recomputed from (m, s) is the term vote_softmax stores.
+__device__ __forceinline__ float vote_softmax_term(float x, float m) { return expf(x - m); }
+__device__ __forceinline__ void vote_softmax_max_sum(const float* v, int nc, float& m, float& s) {
+  m = v[0];
+  for (int q = 1; q < nc; ++q) m = v[q] > m ? v[q] : m;
+  s = 0.0f;
+  for (int q = 0; q < nc; ++q) s += vote_softmax_term(v[q], m);
+}
 __device__ __forceinline__ void vote_softmax(const float* __restrict__ v, int nc, float* p) {
   float m = v[0];
   for (int q = 1; q < nc; ++q) m = v[q] > m ? v[q] : m;
   float s = 0.0f;
-  for (int q = 0; q < nc; ++q) { p[q] = expf(v[q] - m); s += p[q]; }
+  for (int q = 0; q < nc; ++q) { p[q] = vote_softmax_term(v[q], m); s += p[q]; }
   for (int q = 0; q < nc; ++q) p[q] = p[q] / s;
 }
 
