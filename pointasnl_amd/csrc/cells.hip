@@ -21,19 +21,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float LOG2E = 1.4426950408889634f;
 
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-// A value combined across the two halves of the wave (lane l with lane l ^ 32): v_permlane32_swap_b32 with both operands the
-// same register leaves {value of lane l & 31, value of lane (l & 31) + 32} in every lane -- one vector instruction where
-// __shfl_xor(v, 32) is a ds_bpermute_b32 (an LDS round trip).  lo + hi in both halves: the same bits as own + other.
-__device__ __forceinline__ float half_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float half_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// (kappa(r, h), the row index held in register r of lane-half h of a 32x32 MFMA C/D tile: sa_tail.hpp)
+// (fast_exp2, half_max / half_sum and kappa(r, h), the row index held in register r of lane-half h of a 32x32 MFMA C/D tile:
+// sa_tail.hpp, shared with the backward in nl_grad.hip)
 
 // =============================================================================================
 // Non-local attention, MFMA variant with LDS staging ("swapped" flash form, keys split across waves).  The kernel

@@ -443,8 +443,48 @@ def adaptive_sampling_fused(xyz, feature, idx, num_neighbor, scope, bn, weight_d
     return new_xyz, new_feature
 
 
+class _NLAttention(torch.autograd.Function):
+    """nl_attention with the fused deterministic backward (pasnl_cls_nl_attention_grad): saves q, kv and the result, never
+    the (B,P,N) attention map."""
+
+    @staticmethod
+    def forward(ctx, q, kv, variant):
+        q, kv = q.contiguous(), kv.contiguous()
+        out = _nl_attention_forward(q, kv, variant)
+        ctx.save_for_backward(q, kv, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, kv, out = ctx.saved_tensors
+        b, p, cb = q.shape
+        n = kv.shape[1]
+        grad_out = grad_out.contiguous()
+        grad_q = torch.empty_like(q) if ctx.needs_input_grad[0] else None
+        grad_kv = torch.empty_like(kv) if ctx.needs_input_grad[1] else None
+        nbytes = int(_hip.lib().pasnl_cls_nl_attention_grad_workspace_bytes(b, p, n, cb))
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=q.device)
+        _hip.launch("pasnl_cls_nl_attention_grad", "nl_attention_grad", b, p, n, cb, _hip.ptr(q), _hip.ptr(kv), _hip.ptr(out),
+                    _hip.ptr(grad_out), _hip.ptr(grad_q), _hip.ptr(grad_kv), _hip.ptr(ws), ctypes.c_size_t(nbytes))
+        return grad_q, grad_kv, None
+
+
 def nl_attention(q, kv, variant=None):
-    """softmax(q k^T / sqrt(cb)) v with K,V = halves of kv; q (B,P,cb), kv (B,N,2cb) -> (B,P,cb).  Fused."""
+    """softmax(q k^T / sqrt(cb)) v with K,V = halves of kv; q (B,P,cb), kv (B,N,2cb) -> (B,P,cb).  Fused.
+
+    Differentiable in q and kv: with gradients enabled and q or kv requiring one, the result carries a grad_fn whose backward
+    is the fused kernel pair of csrc/nl_grad.hip (no fp atomics, bit-reproducible, 8 B P bytes of workspace).  Otherwise --
+    inference, captured graphs -- this is the plain launch.  PasnlUnsupported (cb outside {32, 64, 128}, unaligned views)
+    propagates as before; callers then take the op-by-op torch chain, which torch differentiates itself.
+    Not differentiable here: the input-space form (pasnl_cls_nl_cell_input) and the fused narrow projections, batch-norm
+    statistics (tf_util with is_training=True), and the AdaptiveSampling cell."""
+    if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
+        return _NLAttention.apply(q, kv, variant)
+    return _nl_attention_forward(q, kv, variant)
+
+
+def _nl_attention_forward(q, kv, variant=None):
     b, p, cb = q.shape
     n = kv.shape[1]
     q, kv = q.contiguous(), kv.contiguous()
