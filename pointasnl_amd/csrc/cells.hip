@@ -19,10 +19,8 @@ namespace pasnl {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr float LOG2E = 1.4426950408889634f;
-
-// (fast_exp2, half_max / half_sum and kappa(r, h), the row index held in register r of lane-half h of a 32x32 MFMA C/D tile:
-// sa_tail.hpp, shared with the backward in nl_grad.hip)
+// (LOG2E and fast_exp2: common.hpp.  half_max / half_sum and kappa(r, h), the row index held in register r of lane-half h of a
+// 32x32 MFMA C/D tile: sa_tail.hpp, shared with the backward in nl_grad.hip)
 
 // =============================================================================================
 // Non-local attention, MFMA variant with LDS staging ("swapped" flash form, keys split across waves).  The kernel

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/pasnl.h"
 
 #define PASNL_WAVE 64
@@ -19,6 +20,10 @@ static inline hipStream_t pasnl_hip_stream(pasnl_stream_t s) { return reinterpre
 namespace pasnl {
 
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// The attention kernels keep their scores in the log2 domain: exp(x - m) == exp2(x * LOG2E - m'), one v_exp_f32.
+constexpr float LOG2E = 1.4426950408889634f;
+__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // DPP controls (GFX9 encoding).
 constexpr int DPP_ROW_SHR1 = 0x111;
@@ -228,6 +233,18 @@ int launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, h
     return PASNL_ELAUNCH;
   hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
   return PASNL_OK;
+}
+
+// f(std::integral_constant<int, S>{}) for the largest power of two S in [LO, HI] that `split` reaches (LO if none): only those
+// kernels are instantiated.
+template <int LO, int HI, class F>
+int with_split(int split, F&& f) {
+  if constexpr (HI > LO) {
+    if (split >= HI) return f(std::integral_constant<int, HI>{});
+    return with_split<LO, HI / 2>(split, f);
+  } else {
+    return f(std::integral_constant<int, LO>{});
+  }
 }
 
 // f(tag) with a long long tag if idx_is_i64, else an int tag: the kNN entries' index type is decltype(tag).

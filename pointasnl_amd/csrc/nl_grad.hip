@@ -348,16 +348,6 @@ static int nlg_split(long tiles, long blocks, int cap) {
 // cb = 64 stays at four waves there too
 template <int CB> constexpr int NLG_QUERY_CAP = CB == 128 ? 4 : 8;
 template <int CB> constexpr int NLG_KEY_CAP = CB == 32 ? 8 : 4;
-// f(integral_constant<split>) for split in {1, 2, 4, 8} up to CAP: only those kernels are instantiated
-template <int CAP, class F>
-static int with_split(int split, F&& f) {
-  if constexpr (CAP >= 8) {
-    if (split >= 8) return f(std::integral_constant<int, 8>{});
-  }
-  if (split >= 4) return f(std::integral_constant<int, 4>{});
-  if (split >= 2) return f(std::integral_constant<int, 2>{});
-  return f(std::integral_constant<int, 1>{});
-}
 
 template <int CB, int SPLIT>
 static int nlg_query_launch(int b, int p, int n, float qscale, float gscale, const float* q, const float* kv, const float* out,
@@ -377,7 +367,7 @@ static int nlg_key_launch(int b, int p, int n, float qscale, float gscale, const
 template <int CB>
 static int nlg_dispatch(int b, int p, int n, const float* q, const float* kv, const float* out, const float* gout, float* grad_q,
                         float* grad_kv, float* lse2, float* delta, hipStream_t st) {
-  const float qscale = 1.4426950408889634f / sqrtf((float)CB), gscale = 1.0f / sqrtf((float)CB);
+  const float qscale = LOG2E / sqrtf((float)CB), gscale = 1.0f / sqrtf((float)CB);
   const long qtiles = (long)b * ((p + NLG_B - 1) / NLG_B), qblocks = (p + NLG_B - 1) / NLG_B;
   const long ktiles = (long)b * ((n + NLG_B - 1) / NLG_B), kblocks = (n + NLG_B - 1) / NLG_B;
   auto query = [&](auto split) {
@@ -387,11 +377,11 @@ static int nlg_dispatch(int b, int p, int n, const float* q, const float* kv, co
     return nlg_key_launch<CB, decltype(split)::value>(b, p, n, qscale, gscale, q, kv, gout, lse2, delta, grad_kv, st);
   };
   const int sq = nlg_split(qtiles, kblocks, NLG_QUERY_CAP<CB>);
-  int rc = with_split<NLG_QUERY_CAP<CB>>(sq, query);
+  int rc = with_split<1, NLG_QUERY_CAP<CB>>(sq, query);
   if (rc != PASNL_OK) return rc;
   if (grad_kv != nullptr) {
     const int sk = nlg_split(ktiles, qblocks, NLG_KEY_CAP<CB>);
-    rc = with_split<NLG_KEY_CAP<CB>>(sk, key);
+    rc = with_split<1, NLG_KEY_CAP<CB>>(sk, key);
     if (rc != PASNL_OK) return rc;
   }
   return pasnl_launch_status();

@@ -9,108 +9,30 @@
 //
 // Three launches, no atomics, every sum in a fixed order:
 //   query-major  nl_input_grad_query_kernel: the forward's structure (one lane per query, 64 queries x SPLIT waves, wave w walks
-//                the w-th range of the cloud's keys through its own LDS region, rows read back as broadcasts).  It recomputes u
-//                as the forward does, sweeps the keys ONCE for (m, l, ctr) -- hence lse and delta -- and a SECOND time for
+//                the w-th range of the cloud's keys through its own LDS region, rows read back as broadcasts), built from the
+//                forward's own pieces (nl_input_core.hpp: projection, staged stream, block step, wave fold).  It recomputes u,
+//                sweeps the keys ONCE for (m, l, ctr) -- hence lse and delta -- and a SECOND time for
 //                du = r sum_j w_j (t_j - delta) X_j: the centred terms are summed as they are, never as the difference of two
-//                large sums, and their own sum corrects delta and du for what h . ctr lost.  It writes dZ, the per-query records (lse in the log2 domain, delta, u, h: 2c + 2 floats) and
-//                the workgroup's partial moments (its queries in ascending order).
+//                large sums, and their own sum corrects delta and du for what h . ctr lost.  It writes dZ, the per-query
+//                records (lse in the log2 domain, delta, u, h: 2c + 2 floats) and the workgroup's partial moments (its
+//                queries in ascending order).
 //   key-major    nl_input_grad_key_kernel: one lane per key, the records of its cloud's queries broadcast from LDS, queries
 //                split over the waves, partial rows folded in ascending wave order -> dX.  Skipped when grad_feature is NULL.
 //   finish       nl_input_grad_finish_kernel: the workgroups' partial moments summed in a fixed order (16 interleaved
 //                ascending runs, then the runs in ascending order) and the c x cb / cz x cb products applied.
 #include <math.h>
-#include <type_traits>
-#include "common.hpp"
+#include "nl_input_core.hpp"
 
 namespace pasnl {
 
-constexpr float NLIG_LOG2E = 1.4426950408889634f;
 constexpr float NLIG_LN2 = 0.6931471805599453f;
 constexpr int NLIG_KB = 8;          // keys per block: one maximum and one rescale in the first sweep, rows read ahead in both
                                     // (the forward's 16 and this kernel's h, delta and lse2 do not fit 16 waves' 128 registers)
 // keys a wave stages at a time (query-major); 16 waves have 128 registers a lane and shorter ranges: half the rows in flight
 constexpr int nlig_key_chunk(int split) { return split == 16 ? 128 : 256; }
-constexpr int NLIG_MIN_ITEMS = 64;  // a wave's range is at least this long before it is split further
 constexpr int NLIG_RUNS = 16;       // interleaved runs of the finish kernel's sums (its waves)
 // what a call needs: the second sweep (du, and the delta of the records); the moments A, s; the moments dWv, dbv
 enum { NLIG_DU = 1, NLIG_A = 2, NLIG_V = 4 };
-
-__device__ __forceinline__ float nlig_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ void nlig_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A wave walks the items [i0, i1) CHUNK at a time through its own LDS region: load(item, row) fetches one item's RW floats
-// (zeros past the range), the next chunk's loads are in flight while use(rows, count) consumes the current one.  No
-// workgroup barrier inside.
-template <int RW, int CHUNK, class Load, class Use>
-__device__ __forceinline__ void nlig_stream(int i0, int i1, float* rows, int lane, Load&& load, Use&& use) {
-  constexpr int RPL = CHUNK / 64;  // rows of a chunk a lane copies
-  float pre[RPL][RW];
-  auto fetch = [&](int ic) {
-#pragma unroll
-    for (int r = 0; r < RPL; ++r) load(ic + r * 64 + lane, pre[r]);
-  };
-  if (i0 < i1) fetch(i0);
-  for (int ic = i0; ic < i1;) {
-#pragma unroll
-    for (int r = 0; r < RPL; ++r)
-#pragma unroll
-      for (int g = 0; g < RW / 4; ++g)
-        *reinterpret_cast<float4*>(rows + (r * 64 + lane) * RW + 4 * g) =
-            make_float4(pre[r][4 * g], pre[r][4 * g + 1], pre[r][4 * g + 2], pre[r][4 * g + 3]);
-    nlig_wave_sync();
-    const int left = i1 - ic;
-    if (left > CHUNK) fetch(ic + CHUNK);
-    use(rows, min(CHUNK, left));
-    nlig_wave_sync();  // every lane has read the chunk before the next one lands on it
-    if (left <= CHUNK) break;
-    ic += CHUNK;
-  }
-}
-
-template <int RW>
-__device__ __forceinline__ void nlig_read_row(const float* rowp, float (&x)[RW]) {
-#pragma unroll
-  for (int g = 0; g < RW / 4; ++g) {
-    const float4 v = *reinterpret_cast<const float4*>(rowp + 4 * g);
-    x[4 * g] = v.x; x[4 * g + 1] = v.y; x[4 * g + 2] = v.z; x[4 * g + 3] = v.w;
-  }
-}
-
-// the forward's block step (nl_input.hip: nli_block): KB staged rows (valid of them are keys if MASK) folded into (m, l, acc)
-template <int CT, int RW, bool MASK>
-__device__ __forceinline__ void nlig_block(const float* rowp, int valid, const float (&u)[CT], float& m, float& l, float (&acc)[CT]) {
-  float x[NLIG_KB][RW], s[NLIG_KB];
-#pragma unroll
-  for (int j = 0; j < NLIG_KB; ++j) nlig_read_row<RW>(rowp + j * RW, x[j]);
-#pragma unroll
-  for (int j = 0; j < NLIG_KB; ++j) {
-    float t = u[0] * x[j][0];
-#pragma unroll
-    for (int ch = 1; ch < CT; ++ch) t = fmaf(u[ch], x[j][ch], t);
-    s[j] = (MASK && j >= valid) ? -INFINITY : t;
-  }
-  float bm = s[0];
-#pragma unroll
-  for (int j = 1; j < NLIG_KB; ++j) bm = fmaxf(bm, s[j]);
-  const float mnew = fmaxf(m, bm);  // finite: key 0 of a block is always valid
-  const float alpha = nlig_exp2(m - mnew);  // m = -inf (nothing seen yet): 0
-  l *= alpha;
-#pragma unroll
-  for (int ch = 0; ch < CT; ++ch) acc[ch] *= alpha;
-#pragma unroll
-  for (int j = 0; j < NLIG_KB; ++j) {
-    const float pj = nlig_exp2(s[j] - mnew);  // masked rows: 0
-    l += pj;
-#pragma unroll
-    for (int ch = 0; ch < CT; ++ch) acc[ch] = fmaf(pj, x[j][ch], acc[ch]);
-  }
-  m = mnew;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // query-major.  CT: channels carried (CT == 3: c == 3 exactly; otherwise any c <= CT, the channels beyond c are zeros).
@@ -148,87 +70,22 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_input_grad_query_kernel(
     mz[threadIdx.x] = t;
   }
 
-  // ---- u = Wk (Z Wq + bq) as the forward forms it, and h = Wv G beside it: the bottleneck's columns in groups of four, dealt
-  // to the waves; the partial sums meet in LDS
+  // ---- the forward's u (scaled) and h = Wv G beside it, then this wave's keys
   float u[CT], h[CT];
-#pragma unroll
-  for (int ch = 0; ch < CT; ++ch) u[ch] = h[ch] = 0.f;
-  for (int kg = wave * 4; kg < cb; kg += SPLIT * 4) {
-    float qv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) qv[j] = bq[kg + j];
-    for (int i = 0; i < cz; ++i) {
-      const float zi = zrow[i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) qv[j] = fmaf(zi, wq[i * cb + kg + j], qv[j]);
-    }
-    const float4 g4 = *reinterpret_cast<const float4*>(grow + kg);
-    const float gv[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-    for (int ch = 0; ch < CT; ++ch)
-      if (CT == 3 || ch < c) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          u[ch] = fmaf(qv[j], wkv[ch * 2 * cb + kg + j], u[ch]);
-          h[ch] = fmaf(gv[j], wkv[ch * 2 * cb + cb + kg + j], h[ch]);
-        }
-      }
-  }
-#pragma unroll
-  for (int ch = 0; ch < CT; ++ch) {
-    park[wave * PARK + ch * 64 + lane] = u[ch];
-    park[wave * PARK + (CT + ch) * 64 + lane] = h[ch];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int ch = 0; ch < CT; ++ch) {
-    float t = park[ch * 64 + lane], th = park[(CT + ch) * 64 + lane];
-    for (int w = 1; w < SPLIT; ++w) {
-      t += park[w * PARK + ch * 64 + lane];
-      th += park[w * PARK + (CT + ch) * 64 + lane];
-    }
-    u[ch] = t * scale;
-    h[ch] = th;
-  }
-  __syncthreads();  // (park is written again at the merges)
-
-  // ---- this wave's keys [k0, k1): whole blocks where the cloud has them
-  const int per = ((n + SPLIT - 1) / SPLIT + NLIG_KB - 1) / NLIG_KB * NLIG_KB;
-  const int k0 = (int)min((long)wave * per, (long)n), k1 = (int)min((long)k0 + per, (long)n);
-  auto load_key = [&](int key, float (&v)[RW]) {
-#pragma unroll
-    for (int ch = 0; ch < RW; ++ch) v[ch] = (ch < CT && key < k1 && (CT == 3 || ch < c)) ? f[(size_t)key * c + ch] : 0.f;
-  };
+  nli_project<CT, SPLIT, PARK, true>(c, cz, cb, scale, zrow, grow, wkv, wq, bq, park, wave, lane, u, h);
+  int k0, k1;
+  nli_key_range<NLIG_KB>(wave, n, SPLIT, k0, k1);
+  auto load_key = [&](int key, float (&v)[RW]) { nli_load_key<CT, RW>(f, key, k1, c, v); };
 
   // ---- first sweep, the forward's online pass: (m, l, sum_j p_j X_j) -> ctr, lse2, delta
   {
     float m = -INFINITY, l = 0.f, acc[CT];
 #pragma unroll
     for (int ch = 0; ch < CT; ++ch) acc[ch] = 0.f;
-    nlig_stream<RW, CHUNK>(k0, k1, rows, lane, load_key, [&](const float* rp, int cnt) {
-      int j0 = 0;
-      for (; j0 + NLIG_KB <= cnt; j0 += NLIG_KB) nlig_block<CT, RW, false>(rp + j0 * RW, NLIG_KB, u, m, l, acc);
-      if (j0 < cnt) nlig_block<CT, RW, true>(rp + j0 * RW, cnt - j0, u, m, l, acc);
-    });
-    if (wave > 0) {
-#pragma unroll
-      for (int ch = 0; ch < CT; ++ch) park[wave * PARK + ch * 64 + lane] = acc[ch];
-      park[wave * PARK + CT * 64 + lane] = m;
-      park[wave * PARK + (CT + 1) * 64 + lane] = l;
-    }
-    __syncthreads();
-    if (wave == 0) {  // ascending wave order; a wave that saw no key has m = -inf, l = 0, acc = 0
-      for (int w = 1; w < SPLIT; ++w) {
-        const float* pw = park + w * PARK;
-        const float mw = pw[CT * 64 + lane], lw = pw[(CT + 1) * 64 + lane];
-        const float mnew = fmaxf(m, mw);
-        const float a0 = m == -INFINITY ? 0.f : nlig_exp2(m - mnew);
-        const float a1 = mw == -INFINITY ? 0.f : nlig_exp2(mw - mnew);
-        l = fmaf(l, a0, lw * a1);
-        m = mnew;
-#pragma unroll
-        for (int ch = 0; ch < CT; ++ch) acc[ch] = fmaf(acc[ch], a0, pw[ch * 64 + lane] * a1);
-      }
+    nli_stream<RW, CHUNK>(k0, k1, rows, lane, load_key,
+                          [&](const float* rp, int cnt) { nli_blocks<NLIG_KB, CT, RW>(rp, cnt, u, m, l, acc); });
+    nli_fold<CT, SPLIT, PARK, true>(park, wave, lane, m, l, acc);
+    if (wave == 0) {
       // (delta = h . ctr is taken from large t_j where one key dominates: ctr keeps every rounding it can -- fused merges, a
       // true division)
       float dl = 0.f;
@@ -255,19 +112,19 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_input_grad_query_kernel(
     for (int ch = 0; ch < CT; ++ch) du[ch] = 0.f;
     auto pair = [&](const float* rowp) {
       float x[RW];
-      nlig_read_row<RW>(rowp, x);
+      nli_read_row<RW>(rowp, x);
       float s = u[0] * x[0], t = h[0] * x[0];
 #pragma unroll
       for (int ch = 1; ch < CT; ++ch) {
         s = fmaf(u[ch], x[ch], s);
         t = fmaf(h[ch], x[ch], t);
       }
-      const float ds = nlig_exp2(s - lse2) * (t - delta);
+      const float ds = fast_exp2(s - lse2) * (t - delta);
       es += ds;
 #pragma unroll
       for (int ch = 0; ch < CT; ++ch) du[ch] = fmaf(ds, x[ch], du[ch]);
     };
-    nlig_stream<RW, CHUNK>(k0, k1, rows, lane, load_key, [&](const float* rp, int cnt) {
+    nli_stream<RW, CHUNK>(k0, k1, rows, lane, load_key, [&](const float* rp, int cnt) {
       int j0 = 0;
       for (; j0 + NLIG_KB <= cnt; j0 += NLIG_KB) {
 #pragma unroll
@@ -373,7 +230,7 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_input_grad_key_kernel(int p, in
   }
   const int per = (p + SPLIT - 1) / SPLIT;
   const int i0 = (int)min((long)wave * per, (long)p), i1 = (int)min((long)i0 + per, (long)p);
-  nlig_stream<RW, CHUNK>(
+  nli_stream<RW, CHUNK>(
       i0, i1, rows, lane,
       [&](int i, float (&v)[RW]) {
         const bool in = i < i1;
@@ -392,14 +249,14 @@ __global__ __launch_bounds__(SPLIT * 64) void nl_input_grad_key_kernel(int p, in
 #pragma unroll 4
         for (int i = 0; i < cnt; ++i) {
           float r[RW];
-          nlig_read_row<RW>(rp + i * RW, r);
+          nli_read_row<RW>(rp + i * RW, r);
           float s = r[0] * x[0], t = r[CT] * x[0];
 #pragma unroll
           for (int ch = 1; ch < CT; ++ch) {
             s = fmaf(r[ch], x[ch], s);
             t = fmaf(r[CT + ch], x[ch], t);
           }
-          const float w = nlig_exp2(s - r[2 * CT]);
+          const float w = fast_exp2(s - r[2 * CT]);
           const float dsl = w * (t - r[2 * CT + 1]) * NLIG_LN2;  // r dS u = dS ln2 (u in the log2 domain)
 #pragma unroll
           for (int ch = 0; ch < CT; ++ch) acc[ch] = fmaf(dsl, r[ch], fmaf(w, r[CT + ch], acc[ch]));
@@ -501,7 +358,7 @@ template <int CT, int SPLIT>
 static int nlig_query_launch(const NligArgs& a, hipStream_t st) {
   const size_t lds = ((size_t)SPLIT * (nlig_key_chunk(SPLIT) * (CT <= 4 ? 4 : 8) + 2 * CT * 64) + (2 * CT + 2) * 64 + 8 * 16) * sizeof(float);
   // scores in the log2 domain, with the forward's own factor: exp(x / sqrt(cb) - m) == exp2(x * log2e / sqrt(cb) - m')
-  const float scale = NLIG_LOG2E / sqrtf((float)a.cb), rs = 1.0f / sqrtf((float)a.cb);
+  const float scale = LOG2E / sqrtf((float)a.cb), rs = 1.0f / sqrtf((float)a.cb);
   return launch(nl_input_grad_query_kernel<CT, SPLIT>, dim3((a.p + 63) / 64, a.b), dim3(SPLIT * 64), lds, st, a.p, a.n, a.c, a.cz,
                 a.cb, scale, rs, a.flags, a.feature, a.new_point, a.wkv, a.wq, a.bq, a.gout,
                 a.grad_x != nullptr ? a.rec : nullptr, a.grad_z, a.part);
@@ -513,28 +370,12 @@ static int nlig_key_launch(const NligArgs& a, hipStream_t st) {
                 a.rec, a.grad_x);
 }
 
-// Waves per workgroup, as nl_input.hip chooses them: the smallest of 4, 8, 16 that puts two waves on every SIMD (2048), as
-// long as a wave keeps NLIG_MIN_ITEMS items (keys for the query-major launch, queries for the key-major one) of its own.
-static int nlig_split(int b, int lanes, int items) {
-  const long tiles = (long)b * ((lanes + 63) / 64);
-  int split = 4;
-  while (split < 16 && tiles * split < 2048 && items / (split * 2) >= NLIG_MIN_ITEMS) split *= 2;
-  return split;
-}
-
+// keys split over the waves of the query-major launch, queries over those of the key-major one
 template <int CT>
 static int nlig_dispatch(const NligArgs& a, hipStream_t st) {
-  // (16 waves are 128 registers a lane: a block of the wide form's rows alone would fill them, so CT == 8 stops at 8 waves)
-  auto with_split = [&](int split, auto&& f) {
-    if constexpr (CT <= 4) {
-      if (split == 16) return f(std::integral_constant<int, 16>{});
-    }
-    if (split >= 8) return f(std::integral_constant<int, 8>{});
-    return f(std::integral_constant<int, 4>{});
-  };
-  int rc = with_split(nlig_split(a.b, a.p, a.n), [&](auto s) { return nlig_query_launch<CT, decltype(s)::value>(a, st); });
+  int rc = nli_with_split<CT>(nli_split(a.b, a.p, a.n), [&](auto s) { return nlig_query_launch<CT, decltype(s)::value>(a, st); });
   if (rc != PASNL_OK || a.grad_x == nullptr) return rc;
-  return with_split(nlig_split(a.b, a.n, a.p), [&](auto s) { return nlig_key_launch<CT, decltype(s)::value>(a, st); });
+  return nli_with_split<CT>(nli_split(a.b, a.n, a.p), [&](auto s) { return nlig_key_launch<CT, decltype(s)::value>(a, st); });
 }
 
 static size_t nlig_record_floats(int b, int p, int c) { return (size_t)(2 * c + 2) * (size_t)b * (size_t)p; }

@@ -10,8 +10,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // row index held in register r of lane-half h of a 32x32 MFMA C/D tile
 __device__ __forceinline__ int kappa(int t, int h) { return (t & 3) + 8 * (t >> 2) + 4 * h; }
 
-// ---- the attention kernels' softmax helpers (cells.hip forward, nl_grad.hip backward)
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+// ---- the MFMA attention kernels' softmax helpers (cells.hip forward, nl_grad.hip backward; fast_exp2: common.hpp)
 // A value combined across the two halves of the wave (lane l with lane l ^ 32): v_permlane32_swap_b32 with both operands the
 // same register leaves {value of lane l & 31, value of lane (l & 31) + 32} in every lane -- one vector instruction where
 // __shfl_xor(v, 32) is a ds_bpermute_b32 (an LDS round trip).  lo + hi in both halves: the same bits as own + other.

@@ -6,7 +6,7 @@ import numpy as np
 from oracle import cells
 
 KB = 16        # keys per softmax block (NLI_KB)
-MIN_KEYS = 64  # NLI_MIN_KEYS
+MIN_KEYS = 64  # NLI_MIN_ITEMS
 LOG2E = np.float32(1.4426950408889634)
 
 _PROBLEMS = {}
@@ -38,7 +38,7 @@ def restated(h, cb):
 
 
 def split_of(b, p, n, c):
-    """waves per workgroup as csrc/nl_input.hip chooses them"""
+    """waves per workgroup: csrc/nl_input_core.hpp's nli_split, capped as its nli_with_split caps the generic width"""
     tiles = b * ((p + 63) // 64)
     split = 4
     while split < 16 and tiles * split < 2048 and n // (split * 2) >= MIN_KEYS:
