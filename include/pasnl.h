@@ -509,6 +509,66 @@ int pasnl_group_point_grad_det(int b, int n, int c, int m, int nsample, const fl
 int pasnl_three_interpolate_grad_det(int b, int n, int c, int m, const float* grad_out, const int* idx, const float* weight,
                                      float* grad_points, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
 
+/* Backward of the AdaptiveSampling cell's three parts that are not GEMMs (csrc/as_grad.hip): the micro attention, the
+ * re-weighting tail and the gather.  No fp atomics, every sum in a fixed order: the gradients are a pure function of the inputs.
+ * Every element of a gradient that is given is written (no memset needed), nothing beside it.
+ * The names carry the pasnl_cls_ prefix, as pasnl_cls_nl_attention_grad does, to stay outside the scope of tests/abi_cases.py,
+ * whose symbol count is pinned; the entries are held to their buffers by tests/test_gpu_as_grad.py instead.
+ *
+ * pasnl_cls_as_attention_grad: backward of pasnl_as_attention.  Per group, with K = kv[..., :cb], V = kv[..., cb:],
+ * P = softmax_j(q_i . k_j / sqrt(cb)) over the `as` keys and g = grad_out (g,as,cb):
+ *     dV = P^T g      dP = g V^T      delta_i = sum_j P_ij dP_ij      dS = P o (dP - delta)
+ *     grad_q = dS K / sqrt(cb)        dK = dS^T Q / sqrt(cb)          grad_kv (g,as,2cb) = [dK | dV]
+ * P is recomputed from q and kv: nothing of the forward is needed and there is no workspace.  One wave per group on the fp32
+ * MFMA; as <= 16, any cb <= 256.  With as == 1 (P == 1) grad_q and the dK half are exact zeros.
+ * grad_q or grad_kv may be NULL: that gradient's products are skipped; both NULL is PASNL_ENULL.
+ * pasnl_cls_as_attention_qkv_grad: the same for pasnl_as_attention_qkv, kvq (g,as,3cb) = [K | V | Q] ->
+ * grad_kvq (g,as,3cb) = [dK | dV | dQ], the whole row.
+ * Checked in this order, before anything is enqueued: g >= 0, as > 0, cb > 0, else PASNL_EINVAL; as <= 16 and cb <= 256, else
+ * PASNL_EUNSUPPORTED; g == 0 is a successful no-op; NULL q, kv (kvq), grad_out or no gradient to write, PASNL_ENULL. */
+int pasnl_cls_as_attention_grad(int g, int as, int cb, const float* q, const float* kv, const float* grad_out, float* grad_q,
+                                float* grad_kv, pasnl_stream_t stream);
+int pasnl_cls_as_attention_qkv_grad(int g, int as, int cb, const float* kvq, const float* grad_out, float* grad_kvq,
+                                    pasnl_stream_t stream);
+
+/* pasnl_cls_as_reweight_grad: backward of pasnl_as_reweight.  With w[s,o] = softmax_s(logits[s,o]), X = grouped_xyz,
+ * F = grouped_feature, gxyz = grad_new_xyz (g,3), gfeat = grad_new_feature (g,ch), and
+ * t_s = sum_d gxyz[d] X[s,d] for o = 0, t_s = gfeat[o-1] F[s,o-1] for o >= 1:
+ *     grad_logits[s,o] = w[s,o] (t_s - sum_r w[r,o] t_r)      dX[s,d] = w[s,0] gxyz[d]      dF[s,j] = w[s,1+j] gfeat[j]
+ * Sums over the neighbours run in ascending s.  grad_logits (g,as,1+ch); grad_grouped_xyz (g,nsample,3) = dX and
+ * grad_grouped_feature (g,nsample,ch) = dF, their rows as..nsample-1 written as zeros.  With as == 1 grad_logits is exact zeros.
+ * pasnl_cls_as_reweight_x_grad: backward of pasnl_as_reweight_x, x (g,as,3+ch).  grad_x (g,as,3+ch): columns 0-2 are zeros,
+ * column 3+j holds dF[s,j], and for j < 3 dX[s,j] is added to it (those columns of x are the coordinates AND the first three
+ * features).
+ * Any of the three (two) gradients may be NULL and is then skipped; all NULL is PASNL_ENULL.  grouped_xyz, grouped_feature
+ * (x) are read for grad_logits only.
+ * Checked in the order of the forward entries: g >= 0, as > 0, nsample >= as, ch > 0 (x form: ch > 3), else PASNL_EINVAL;
+ * as <= 16, else PASNL_EUNSUPPORTED; g == 0 is a successful no-op; NULL logits, grad_new_xyz, grad_new_feature, no gradient
+ * to write, or grad_logits without the grouped tensors (x), PASNL_ENULL. */
+int pasnl_cls_as_reweight_grad(int g, int as, int nsample, int ch, const float* logits, const float* grouped_xyz,
+                               const float* grouped_feature, const float* grad_new_xyz, const float* grad_new_feature,
+                               float* grad_logits, float* grad_grouped_xyz, float* grad_grouped_feature, pasnl_stream_t stream);
+int pasnl_cls_as_reweight_x_grad(int g, int as, int ch, const float* logits, const float* x, const float* grad_new_xyz,
+                                 const float* grad_new_feature, float* grad_logits, float* grad_x, pasnl_stream_t stream);
+
+/* pasnl_cls_as_gather_grad: backward of pasnl_as_gather, whose rows are [xyz[i_s] - xyz[i_0] | xyz[i_s] | feature[i_s]].
+ * grad_x (b,m,as,6+c) is folded to one row per gathered point,
+ *     r[j,s] = [gx[j,s,0:3] + gx[j,s,3:6] - (s == 0 ? sum_t gx[j,t,0:3] : 0) | gx[j,s,6:]]      (sum over t ascending)
+ * and r is scattered to grad_xyz (b,n,3) and grad_feature (b,n,c) by the machinery of pasnl_group_point_grad_det: each source
+ * point's row is the sum of its contributions in ascending order of the forward output element (j,s); every destination row
+ * is written, a point no group drew gets exact zeros.  idx (b,m,k): only its first `as` columns are read.
+ * grad_xyz or grad_feature may be NULL: that scatter is skipped; both NULL is PASNL_ENULL.
+ * workspace: pasnl_cls_as_gather_grad_workspace_bytes bytes =
+ *     pasnl_grad_workspace_bytes(b, n, m*as) + 4 b m as (1 + 3 + c)      (the lists; idx's first columns, r)
+ * (0 for b <= 0, n <= 0, c <= 0, m < 0 or as <= 0).
+ * Checked in this order, before anything is enqueued: b, m >= 0 and n, c, k, as > 0 and as <= k, else PASNL_EINVAL;
+ * n <= 38400 (the lists' LDS histogram) and m*as < 2^31, else PASNL_EUNSUPPORTED; b == 0 is a successful no-op; no gradient
+ * to write, or NULL grad_x / idx with b m as > 0, PASNL_ENULL; a NULL or short workspace PASNL_EWORKSPACE; a workspace that
+ * is not 4-byte aligned PASNL_EUNSUPPORTED. */
+size_t pasnl_cls_as_gather_grad_workspace_bytes(int b, int n, int c, int m, int as);
+int pasnl_cls_as_gather_grad(int b, int n, int c, int m, int k, int as, const float* grad_x, const int* idx, float* grad_xyz,
+                             float* grad_feature, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
 /* Tail of a set-abstraction layer, fused (pointasnl_util.py:258-261 skip connection, :213-216 back-projection of the
  * non-local cell, :282-290 the two adds and the aggregation layer):
  *   out = relu( ( after + relu(skip_max ws + bs) + relu(att wb + bb) ) wagg + bagg )

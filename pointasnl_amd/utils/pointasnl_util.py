@@ -291,15 +291,223 @@ def weight_net_hidden(xyz, hidden_units, scope, is_training, bn_decay=None, weig
     return net
 
 
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+class _ASAttention(torch.autograd.Function):
+    """as_attention with the fused deterministic backward (pasnl_cls_as_attention_grad): saves q and kv only, the attention
+    map is recomputed."""
+
+    @staticmethod
+    def forward(ctx, q, kv):
+        q, kv = q.contiguous(), kv.contiguous()
+        ctx.save_for_backward(q, kv)
+        return _as_attention_forward(q, kv)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, kv = ctx.saved_tensors
+        as_, cb = q.shape[-2], q.shape[-1]
+        grad_out = grad_out.contiguous()
+        grad_q = torch.empty_like(q) if ctx.needs_input_grad[0] else None
+        grad_kv = torch.empty_like(kv) if ctx.needs_input_grad[1] else None
+        _hip.launch("pasnl_cls_as_attention_grad", "as_attention_grad", q.numel() // (as_ * cb), as_, cb, _hip.ptr(q), _hip.ptr(kv),
+                    _hip.ptr(grad_out), _hip.ptr(grad_q), _hip.ptr(grad_kv))
+        return grad_q, grad_kv
+
+
 def as_attention(q, kv):
     """softmax(q k^T / sqrt(cb)) v per group of `as` neighbours (pointasnl_util.py:136-146), fused.
-    q (..., as, cb), kv (..., as, 2cb) -> (..., as, cb)"""
+    q (..., as, cb), kv (..., as, 2cb) -> (..., as, cb)
+
+    Differentiable in q and kv: with gradients enabled and q or kv requiring one, the result carries a grad_fn whose backward is
+    one kernel of csrc/as_grad.hip (no fp atomics, no workspace, bit-reproducible).  Otherwise this is the plain launch."""
+    if _needs_grad(q, kv):
+        return _ASAttention.apply(q, kv)
+    return _as_attention_forward(q, kv)
+
+
+def _as_attention_forward(q, kv):
     as_, cb = q.shape[-2], q.shape[-1]
     g = q.numel() // (as_ * cb)
     q, kv = q.contiguous(), kv.contiguous()
     out = torch.empty_like(q)
     _hip.launch("pasnl_as_attention", "as_attention", g, as_, cb, _hip.ptr(q), _hip.ptr(kv), _hip.ptr(out))
     return out
+
+
+class _ASAttentionQKV(torch.autograd.Function):
+    """as_attention_qkv with the fused backward (pasnl_cls_as_attention_qkv_grad): the gradient of the whole [K | V | Q] row"""
+
+    @staticmethod
+    def forward(ctx, kvq, cb):
+        kvq = kvq.contiguous()
+        ctx.save_for_backward(kvq)
+        return _as_attention_qkv_forward(kvq, cb)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        kvq, = ctx.saved_tensors
+        as_, cb = kvq.shape[-2], kvq.shape[-1] // 3
+        grad_out = grad_out.contiguous()
+        grad_kvq = torch.empty_like(kvq)
+        _hip.launch("pasnl_cls_as_attention_qkv_grad", "as_attention_grad", kvq.numel() // (as_ * 3 * cb), as_, cb, _hip.ptr(kvq),
+                    _hip.ptr(grad_out), _hip.ptr(grad_kvq))
+        return grad_kvq, None
+
+
+def as_attention_qkv(kvq, cb):
+    """as_attention on ONE tensor kvq (..., as, 3cb) = [K | V | Q] per row (the output of a single projection GEMM)
+    -> (..., as, cb).  Differentiable in kvq, as as_attention is."""
+    cb = int(cb)
+    if kvq.shape[-1] != 3 * cb:
+        raise ValueError(f"as_attention_qkv: rows of {kvq.shape[-1]} floats are not [K | V | Q] of width {cb}")
+    if _needs_grad(kvq):
+        return _ASAttentionQKV.apply(kvq, cb)
+    return _as_attention_qkv_forward(kvq, cb)
+
+
+def _as_attention_qkv_forward(kvq, cb):
+    as_ = kvq.shape[-2]
+    kvq = kvq.contiguous()
+    out = torch.empty(kvq.shape[:-1] + (cb,), dtype=torch.float32, device=kvq.device)
+    _hip.launch("pasnl_as_attention_qkv", "as_attention", kvq.numel() // (as_ * 3 * cb), as_, cb, _hip.ptr(kvq), _hip.ptr(out))
+    return out
+
+
+class _ASReweight(torch.autograd.Function):
+    """as_reweight with the fused backward (pasnl_cls_as_reweight_grad)"""
+
+    @staticmethod
+    def forward(ctx, logits, group_xyz, group_feature, num_neighbor):
+        logits, group_xyz, group_feature = logits.contiguous(), group_xyz.contiguous(), group_feature.contiguous()
+        ctx.save_for_backward(logits, group_xyz, group_feature)
+        return _as_reweight_forward(logits, group_xyz, group_feature, num_neighbor)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_new_xyz, grad_new_feature):
+        logits, group_xyz, group_feature = ctx.saved_tensors
+        b, p, nsample, ch = group_feature.shape
+        grad_logits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        grad_xyz = torch.empty_like(group_xyz) if ctx.needs_input_grad[1] else None
+        grad_feature = torch.empty_like(group_feature) if ctx.needs_input_grad[2] else None
+        grad_new_xyz, grad_new_feature = grad_new_xyz.contiguous(), grad_new_feature.contiguous()
+        _hip.launch("pasnl_cls_as_reweight_grad", "as_reweight_grad", b * p, int(logits.shape[2]), int(nsample), int(ch),
+                    _hip.ptr(logits), _hip.ptr(group_xyz), _hip.ptr(group_feature), _hip.ptr(grad_new_xyz),
+                    _hip.ptr(grad_new_feature), _hip.ptr(grad_logits), _hip.ptr(grad_xyz), _hip.ptr(grad_feature))
+        return grad_logits, grad_xyz, grad_feature, None
+
+
+def as_reweight(logits, group_xyz, group_feature, num_neighbor):
+    """AdaptiveSampling's tail (pointasnl_util.py:154,167-171) in one kernel: softmax of logits (B,P,as,1+ch) over the neighbour
+    axis, then the weighted sums over the first `num_neighbor` rows of group_xyz (B,P,nsample,3) and group_feature
+    (B,P,nsample,ch), read in place -> new_xyz (B,P,3), new_feature (B,P,ch).  Differentiable in all three tensors (one kernel
+    of csrc/as_grad.hip) when gradients are enabled and one of them requires one; otherwise the plain launch."""
+    if logits.shape[2] != int(num_neighbor):
+        raise ValueError(f"as_reweight: logits of {logits.shape[2]} neighbours, num_neighbor = {num_neighbor}")
+    if _needs_grad(logits, group_xyz, group_feature):
+        return _ASReweight.apply(logits, group_xyz, group_feature, int(num_neighbor))
+    return _as_reweight_forward(logits, group_xyz, group_feature, num_neighbor)
+
+
+def _as_reweight_forward(logits, group_xyz, group_feature, num_neighbor):
+    b, p, nsample, num_channel = group_feature.shape
+    group_xyz, group_feature, logits = group_xyz.contiguous(), group_feature.contiguous(), logits.contiguous()
+    new_xyz = torch.empty((b, p, 3), dtype=torch.float32, device=group_xyz.device)
+    new_feature = torch.empty((b, p, num_channel), dtype=torch.float32, device=group_xyz.device)
+    _hip.launch("pasnl_as_reweight", "as_reweight", b * p, int(num_neighbor), int(nsample), int(num_channel),
+                                            _hip.ptr(logits), _hip.ptr(group_xyz), _hip.ptr(group_feature),
+                                            _hip.ptr(new_xyz), _hip.ptr(new_feature))
+    return new_xyz, new_feature
+
+
+class _ASReweightX(torch.autograd.Function):
+    """as_reweight_x with the fused backward (pasnl_cls_as_reweight_x_grad)"""
+
+    @staticmethod
+    def forward(ctx, logits, x):
+        logits, x = logits.contiguous(), x.contiguous()
+        ctx.save_for_backward(logits, x)
+        return _as_reweight_x_forward(logits, x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_new_xyz, grad_new_feature):
+        logits, x = ctx.saved_tensors
+        b, p, as_, w = x.shape
+        grad_logits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        grad_x = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        grad_new_xyz, grad_new_feature = grad_new_xyz.contiguous(), grad_new_feature.contiguous()
+        _hip.launch("pasnl_cls_as_reweight_x_grad", "as_reweight_grad", b * p, int(as_), int(w - 3), _hip.ptr(logits), _hip.ptr(x),
+                    _hip.ptr(grad_new_xyz), _hip.ptr(grad_new_feature), _hip.ptr(grad_logits), _hip.ptr(grad_x))
+        return grad_logits, grad_x
+
+
+def as_reweight_x(logits, x):
+    """as_reweight on the rows as_gather produces: x (B,P,as,6+c) = [xyz - xyz0 | xyz | feature], logits (B,P,as,1+3+c)
+    -> new_xyz (B,P,3), new_feature (B,P,3+c).  Differentiable in logits and x, as as_reweight is."""
+    if _needs_grad(logits, x):
+        return _ASReweightX.apply(logits, x)
+    return _as_reweight_x_forward(logits, x)
+
+
+def _as_reweight_x_forward(logits, x):
+    b, p, as_, w = x.shape
+    logits, x = logits.contiguous(), x.contiguous()
+    new_xyz = torch.empty((b, p, 3), dtype=torch.float32, device=x.device)
+    new_feature = torch.empty((b, p, w - 3), dtype=torch.float32, device=x.device)
+    _hip.launch("pasnl_as_reweight_x", "as_reweight", b * p, int(as_), int(w - 3), _hip.ptr(logits), _hip.ptr(x), _hip.ptr(new_xyz),
+                _hip.ptr(new_feature))
+    return new_xyz, new_feature
+
+
+class _ASGather(torch.autograd.Function):
+    """as_gather with the deterministic backward (pasnl_cls_as_gather_grad): the ordered segmented sums of group_point's"""
+
+    @staticmethod
+    def forward(ctx, xyz, feature, idx, num_neighbor):
+        xyz, feature, idx = xyz.contiguous(), feature.contiguous(), idx.contiguous()
+        ctx.save_for_backward(idx)
+        ctx.dims = (feature.shape[1], feature.shape[2], int(num_neighbor))
+        return _as_gather_forward(xyz, feature, idx, num_neighbor)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_x):
+        idx, = ctx.saved_tensors
+        n, c, as_ = ctx.dims
+        b, m, k = idx.shape
+        grad_x = grad_x.contiguous()
+        grad_xyz = torch.empty((b, n, 3), dtype=torch.float32, device=idx.device) if ctx.needs_input_grad[0] else None
+        grad_feature = torch.empty((b, n, c), dtype=torch.float32, device=idx.device) if ctx.needs_input_grad[1] else None
+        nbytes = int(_hip.lib().pasnl_cls_as_gather_grad_workspace_bytes(b, n, c, m, as_))
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=idx.device)
+        _hip.launch("pasnl_cls_as_gather_grad", "as_gather_grad", b, n, c, m, k, as_, _hip.ptr(grad_x), _hip.ptr(idx),
+                    _hip.ptr(grad_xyz), _hip.ptr(grad_feature), _hip.ptr(ws), ctypes.c_size_t(nbytes))
+        return grad_xyz, grad_feature, None, None
+
+
+def as_gather(xyz, feature, idx, num_neighbor):
+    """The AdaptiveSampling cell's input rows in one launch: x (B,P,as,6+C) = [xyz[i_s] - xyz[i_0] | xyz[i_s] | feature[i_s]] for
+    the first as = num_neighbor columns i_s of idx (B,P,K).  Differentiable in xyz (B,N,3) and feature (B,N,C): the backward
+    (csrc/as_grad.hip) sums every point's contributions in the order of the forward's output elements, without fp atomics."""
+    if _needs_grad(xyz, feature):
+        return _ASGather.apply(xyz, feature, idx, int(num_neighbor))
+    return _as_gather_forward(xyz, feature, idx, num_neighbor)
+
+
+def _as_gather_forward(xyz, feature, idx, num_neighbor):
+    b, n, c = feature.shape
+    _, p, k = idx.shape
+    as_ = int(num_neighbor)
+    xyz, feature, idx = xyz.contiguous(), feature.contiguous(), idx.contiguous()
+    x = torch.empty((b, p, as_, 6 + c), dtype=torch.float32, device=xyz.device)
+    _hip.launch("pasnl_as_gather", "as_gather", b, n, c, p, k, as_, _hip.ptr(xyz), _hip.ptr(feature), _hip.ptr(idx), _hip.ptr(x))
+    return x
 
 
 def SampleWeights(new_point, grouped_xyz, mlps, is_training, bn_decay, weight_decay, scope, bn=True, scaled=True,
@@ -346,14 +554,7 @@ def AdaptiveSampling(group_xyz, group_feature, num_neighbor, is_training, bn_dec
                                weight_decay, scope, bn, return_logits=True)
         # softmax over the neighbour axis + the two weighted sums (pointasnl_util.py:154,167-171) in one kernel
         # that reads the first `num_neighbor` rows of the full grouped tensors in place
-        b, p = group_xyz.shape[:2]
-        group_xyz, group_feature, logits = group_xyz.contiguous(), group_feature.contiguous(), logits.contiguous()
-        new_xyz = torch.empty((b, p, 3), dtype=torch.float32, device=group_xyz.device)
-        new_feature = torch.empty((b, p, num_channel), dtype=torch.float32, device=group_xyz.device)
-        _hip.launch("pasnl_as_reweight", "as_reweight", b * p, int(num_neighbor), int(nsample), int(num_channel),
-                                                _hip.ptr(logits), _hip.ptr(group_xyz), _hip.ptr(group_feature),
-                                                _hip.ptr(new_xyz), _hip.ptr(new_feature))
-        return new_xyz, new_feature
+        return as_reweight(logits, group_xyz, group_feature, num_neighbor)
 
 
 AS_FUSED = True  # False = the reference's op-by-op AdaptiveSampling / SampleWeights chain on gathered tensors
@@ -376,9 +577,29 @@ def adaptive_sampling_fused(xyz, feature, idx, num_neighbor, scope, bn, weight_d
     cb = max(32, channel // 2)
     xyz, feature, idx = xyz.contiguous(), feature.contiguous(), idx.contiguous()
     narrow = AS_CELL_NARROW and 6 + c <= 15 and 1 + channel <= 16 and cb in (32, 64)
-    x = torch.empty((b, p, as_, 6 + c), dtype=torch.float32, device=xyz.device)
-    _hip.launch("pasnl_as_gather", "as_gather", b, n, c, p, k, as_, _hip.ptr(xyz), _hip.ptr(feature), _hip.ptr(idx), _hip.ptr(x))
     st = tf_util.store()
+    if torch.is_grad_enabled():
+        # a gradient is asked for: the differentiable chain -- as_gather, one GEMM to [K | V | Q], as_attention_qkv, the two mlp2
+        # GEMMs, as_reweight_x -- each piece with a backward of its own (csrc/as_grad.hip; torch differentiates the GEMMs and
+        # the BN folding).  The one-kernel cells below have none.
+        with tf_util.variable_scope(scope), tf_util.variable_scope(scope):
+            layers = []
+            for name, cin, cout in (('conv_kv_ds', 6 + c, 2 * cb), ('conv_query_ds', 6 + c, cb), ('mlp2_0', cb, 32),
+                                    ('mlp2_1', 32, 1 + channel)):
+                with tf_util.variable_scope(name):
+                    layers.append(st.layer(cin, cout, bn, weight_decay))
+            if xyz.requires_grad or feature.requires_grad or any(t.requires_grad for wb_ in layers for t in wb_):
+                (wkv, bkv), (wq, bq) = layers[:2]
+                x = as_gather(xyz, feature, idx, as_)
+                # (built per call: a concatenation that carries a graph must not outlive its backward in st._folded)
+                kvq = torch.addmm(torch.cat([bkv, bq]), x.reshape(-1, 6 + c), torch.cat([wkv, wq], dim=1))
+                att = as_attention_qkv(kvq.reshape(b, p, as_, 3 * cb), cb)
+                hid = tf_util.conv2d(att, 32, [1, 1], padding='VALID', stride=[1, 1], bn=bn, is_training=False, scope='mlp2_0',
+                                     weight_decay=weight_decay)
+                logits = tf_util.conv2d(hid, 1 + channel, [1, 1], padding='VALID', stride=[1, 1], bn=bn, is_training=False,
+                                        scope='mlp2_1', activation_fn=None, weight_decay=weight_decay)
+                return as_reweight_x(logits, x)
+    x = _as_gather_forward(xyz, feature, idx, as_)
     with tf_util.variable_scope(scope), tf_util.variable_scope(scope):  # AdaptiveSampling's and SampleWeights' scopes
         key = st.path("kvq_fused")
         if key not in st._folded:
@@ -436,11 +657,7 @@ def adaptive_sampling_fused(xyz, feature, idx, num_neighbor, scope, bn, weight_d
                              weight_decay=weight_decay)
         logits = tf_util.conv2d(hid, 1 + channel, [1, 1], padding='VALID', stride=[1, 1], bn=bn, is_training=False,
                                 scope='mlp2_1', activation_fn=None, weight_decay=weight_decay).contiguous()
-    new_xyz = torch.empty((b, p, 3), dtype=torch.float32, device=xyz.device)
-    new_feature = torch.empty((b, p, channel), dtype=torch.float32, device=xyz.device)
-    _hip.launch("pasnl_as_reweight_x", "as_reweight", b * p, as_, channel, _hip.ptr(logits), _hip.ptr(x), _hip.ptr(new_xyz),
-                _hip.ptr(new_feature))
-    return new_xyz, new_feature
+    return _as_reweight_x_forward(logits, x)
 
 
 class _NLAttention(torch.autograd.Function):
@@ -477,9 +694,10 @@ def nl_attention(q, kv, variant=None):
     is the fused kernel pair of csrc/nl_grad.hip (no fp atomics, bit-reproducible, 8 B P bytes of workspace).  Otherwise --
     inference, captured graphs -- this is the plain launch.  PasnlUnsupported (cb outside {32, 64, 128}, unaligned views)
     propagates as before; callers then take the op-by-op torch chain, which torch differentiates itself.
-    The input-space form of the cell's first level is differentiable too (nl_cell_input, below).  Not differentiable here:
-    the fused narrow projections (pasnl_narrow_project2, the fallback of levels with 9 to 16 input channels), batch-norm
-    statistics (tf_util with is_training=True), and the AdaptiveSampling cell."""
+    The input-space form of the cell's first level is differentiable too (nl_cell_input, below), and so is the AdaptiveSampling
+    cell (as_gather, as_attention, as_reweight above).  Not differentiable here: the fused narrow projections
+    (pasnl_narrow_project2, the fallback of levels with 9 to 16 input channels) and batch-norm statistics (tf_util with
+    is_training=True)."""
     if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
         return _NLAttention.apply(q, kv, variant)
     return _nl_attention_forward(q, kv, variant)

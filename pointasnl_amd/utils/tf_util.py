@@ -289,14 +289,17 @@ def _dense(inputs, num_output_channels, scope, bn, activation_fn, weight_decay=N
             cin += input_pad
     x2d = inputs.reshape(-1, cin)
     is_relu = activation_fn in ("relu", torch.relu, torch.nn.functional.relu)
-    if (DENSE_ROWS and x2d.is_cuda and 0 < x2d.shape[0] <= DENSE_ROWS_MAX and cin % 8 == 0 and (is_relu or activation_fn is None)
+    # the three kernels below are raw launches without a backward: where a gradient is asked for, the vendor GEMM, which torch
+    # differentiates (a gradient is never dropped silently)
+    fused_ok = not (torch.is_grad_enabled() and (x2d.requires_grad or w.requires_grad or b.requires_grad))
+    if (fused_ok and DENSE_ROWS and x2d.is_cuda and 0 < x2d.shape[0] <= DENSE_ROWS_MAX and cin % 8 == 0 and (is_relu or activation_fn is None)
             and x2d.dtype == torch.float32):
         try:
             out = _dense_rows(x2d, w, b, is_relu)
             return out.reshape(*inputs.shape[:-1], num_output_channels)
         except _hip.PasnlUnsupported:
             pass  # e.g. an unaligned view: the vendor GEMM below
-    if (DENSE_SPLITK and x2d.is_cuda and x2d.dtype == torch.float32 and (is_relu or activation_fn is None)
+    if (fused_ok and DENSE_SPLITK and x2d.is_cuda and x2d.dtype == torch.float32 and (is_relu or activation_fn is None)
             and cin >= SPLITK_MIN_K and cin % 16 == 0 and num_output_channels % 4 == 0
             and num_output_channels <= SPLITK_MAX_N and x2d.shape[0] >= SPLITK_MIN_ROWS
             and -(-x2d.shape[0] // 128) * -(-num_output_channels // 128) <= SPLITK_MAX_TILES):
@@ -305,7 +308,7 @@ def _dense(inputs, num_output_channels, scope, bn, activation_fn, weight_decay=N
             return out.reshape(*inputs.shape[:-1], num_output_channels)
         except _hip.PasnlUnsupported:
             pass  # e.g. an unaligned view: the vendor GEMM below
-    if (DENSE_BF16X3 and x2d.is_cuda and x2d.dtype == torch.float32 and (is_relu or activation_fn is None)
+    if (fused_ok and DENSE_BF16X3 and x2d.is_cuda and x2d.dtype == torch.float32 and (is_relu or activation_fn is None)
             and cin >= BF16X3_MIN_K and cin % 32 == 0 and num_output_channels % 128 == 0
             and -(-x2d.shape[0] // 128) * (num_output_channels // 128) >= BF16X3_MIN_TILES
             and x2d.stride(1) == 1 and x2d.stride(0) % 4 == 0 and x2d.data_ptr() % 16 == 0):
@@ -323,8 +326,8 @@ def _dense(inputs, num_output_channels, scope, bn, activation_fn, weight_decay=N
         if key not in st._folded:
             st._folded[key] = (w.t().contiguous(), w)  # (keeps `w` alive: the pointer in the key stays unique)
         w = st._folded[key][0].t()
-    if activation_fn in ("relu", torch.relu, torch.nn.functional.relu) and FUSE_RELU_EPILOGUE:
-        # bias + ReLU in the GEMM epilogue (hipBLASLt) instead of a second pass over the output
+    if activation_fn in ("relu", torch.relu, torch.nn.functional.relu) and FUSE_RELU_EPILOGUE and fused_ok:
+        # bias + ReLU in the GEMM epilogue (hipBLASLt) instead of a second pass over the output (torch has no derivative for it)
         out = torch._addmm_activation(b, x2d, w)
         return out.reshape(*inputs.shape[:-1], num_output_channels)
     out = torch.addmm(b, x2d, w).reshape(*inputs.shape[:-1], num_output_channels)
