@@ -569,6 +569,64 @@ size_t pasnl_cls_as_gather_grad_workspace_bytes(int b, int n, int c, int m, int 
 int pasnl_cls_as_gather_grad(int b, int n, int c, int m, int k, int as, const float* grad_x, const int* idx, float* grad_xyz,
                              float* grad_feature, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
 
+/* Backward of a set-abstraction layer's grouping and local cell (csrc/sa_grad.hip).  No fp atomics, every sum in a fixed order
+ * that depends on the arguments alone (never on the device): the gradients are a pure function of the inputs.  Every element of
+ * a gradient that is given is written (no memset needed), nothing beside it.  (pasnl_cls_ prefix: see above.)
+ *
+ * pasnl_cls_sa_local_cell_grad: backward of pasnl_sa_local_cell.  Per group, X = x[g] (k,w), dM = grad_out[g] (c2,32), and the
+ * forward's H1 = relu(X W0 + b0), H2 = relu(H1 W1 + b1), G = relu(X[:,0:3] Ww + bw) recomputed (nothing of the forward is saved):
+ *     dH2 = G dM^T     dG = H2 dM     dZ2 = dH2 o [H2 > 0]     dZg = dG o [G > 0]     dH1 = dZ2 W1^T     dZ1 = dH1 o [H1 > 0]
+ *     grad_x = dZ1 W0^T,  grad_x[:,0:3] += dZg Ww^T
+ *     grad_w1 = sum H1^T dZ2     grad_b1 = sum dZ2     grad_w0 = sum X^T dZ1     grad_b0 = sum dZ1
+ *     grad_ww = sum X[:,0:3]^T dZg     grad_bw = sum dZg                        (sums over all groups and rows)
+ * Shapes as the forward's: grad_x (groups,k,w), grad_w0 (w,c1), grad_b0 (c1), grad_w1 (c1,c2), grad_b1 (c2), grad_ww (3,32),
+ * grad_bw (32).  One wave per group on the fp32 32x32x2 MFMA, weights in LDS.  The weight gradients are accumulated in
+ * registers by min(groups, 1024) waves, wave s taking groups s, s + slots, ...; each flushes one partial slot and a second
+ * launch sums the slots in ascending order.
+ * Supported: k % 32 == 0, (c1,c2) = (32,32) or (64,64), 3 <= w <= 96.  Every kernel keeps its accumulators in registers (no
+ * scratch); where the weight-gradient accumulators and grad_x's tiles do not fit the register file together -- (32,32) with
+ * w > 64, (64,64) with w > 32 -- the call is two or three launches of the first kernel, each producing a part ({dW1, db1, dWw,
+ * dbw}, {dW0, db0}, grad_x) from its own recomputed forward: the same bits as one launch.  Wider cells (128 and up), c1 != c2
+ * and wider rows are PASNL_EUNSUPPORTED (the Python mirror then differentiates the op-by-op chain).
+ * Any gradient pointer may be NULL.  grad_x == NULL skips the product dZ1 W0^T; with no weight gradient at all there are no
+ * partials, no row-p transposes, no second launch and the workspace is not touched (it may be NULL); in a one-launch form the
+ * six weight gradients are accumulated together and a NULL one among them is only not written, in the three-launch form a part
+ * none of whose gradients is asked for is not run.  All seven NULL is PASNL_ENULL.
+ * workspace: pasnl_cls_sa_local_cell_grad_workspace_bytes(groups, w, c1, c2) bytes =
+ *     4 min(groups, 1024) (w c1 + c1 + c1 c2 + c2 + 96 + 32)        (0 for groups <= 0, w < 3, c1 <= 0 or c2 <= 0)
+ * Checked in this order, before anything is enqueued: groups >= 0, k > 0, w >= 3, c1, c2 > 0, else PASNL_EINVAL; the supported
+ * set above, else PASNL_EUNSUPPORTED; groups == 0 zero-fills the weight gradients given and is done; NULL x, a weight, a bias,
+ * grad_out, or no gradient to write, PASNL_ENULL; with a weight gradient asked for, a workspace that is not 4-byte aligned
+ * PASNL_EUNSUPPORTED, then a NULL or short one PASNL_EWORKSPACE. */
+size_t pasnl_cls_sa_local_cell_grad_workspace_bytes(int groups, int w, int c1, int c2);
+int pasnl_cls_sa_local_cell_grad(int groups, int k, int w, int c1, int c2, const float* x, const float* w0, const float* b0,
+                                 const float* w1, const float* b1, const float* ww, const float* bw, const float* grad_out,
+                                 float* grad_x, float* grad_w0, float* grad_b0, float* grad_w1, float* grad_b1, float* grad_ww,
+                                 float* grad_bw, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
+/* pasnl_cls_sa_group_grad: backward of pasnl_sa_group, new_point[j,s] = [xyz[i] - new_xyz[j] | xyz[i] | feature[i]],
+ * i = idx[b,j,s], skip[j] = max_s new_point[j,s].  grad_new_point (b,m,k,6+c) and grad_skip (b,m,6+c); either may be NULL and
+ * then counts as zeros.  The maximum follows TensorFlow's reduce_max rule: every element equal to its column's maximum gets
+ * grad_skip / count, the comparison made on the forward's own float32 values (recomputed with the forward's expression).  With
+ * e[j,s] = grad_new_point[j,s] + share[j,s]:
+ *     r[j,s] = [e[0:3] + e[3:6] | e[6:]]          grad_new_xyz[j] = -sum_s e[j,s,0:3]      (s ascending)
+ * and r is scattered to grad_xyz (b,n,3) and grad_feature (b,n,c) by the machinery of pasnl_group_point_grad_det: each source
+ * point's row is the sum of its contributions in ascending order of (j,s); an index drawn twice in a group shares and then
+ * re-sums at its point; every destination row is written, a point no group drew gets exact zeros.  grad_new_xyz (b,m,3).
+ * Each of the three gradients may be NULL and is then skipped; all NULL is PASNL_ENULL.
+ * workspace: pasnl_cls_sa_group_grad_workspace_bytes(b, n, c, m, k) bytes =
+ *     pasnl_grad_workspace_bytes(b, n, m*k) + 4 b m k (3 + c)                  (the lists; r)
+ * (0 for b <= 0, n <= 0, c <= 0, m < 0 or k <= 0); not touched, and may be NULL, when only grad_new_xyz is asked for.
+ * Checked in this order, before anything is enqueued: b, m >= 0 and n, c, k > 0, else PASNL_EINVAL; n <= 38400 (the lists' LDS
+ * histogram), m*k < 2^31 and b*m < 2^31, else PASNL_EUNSUPPORTED; b == 0 is a successful no-op; no gradient to write, or NULL
+ * xyz / feature / idx / new_xyz with b m k > 0, PASNL_ENULL; with a scatter asked for, a workspace that is not 4-byte aligned
+ * PASNL_EUNSUPPORTED, then a NULL or short one PASNL_EWORKSPACE. */
+size_t pasnl_cls_sa_group_grad_workspace_bytes(int b, int n, int c, int m, int k);
+int pasnl_cls_sa_group_grad(int b, int n, int c, int m, int k, const float* xyz, const float* feature, const int* idx,
+                            const float* new_xyz, const float* grad_new_point, const float* grad_skip, float* grad_xyz,
+                            float* grad_feature, float* grad_new_xyz, void* workspace, size_t workspace_bytes,
+                            pasnl_stream_t stream);
+
 /* Tail of a set-abstraction layer, fused (pointasnl_util.py:258-261 skip connection, :213-216 back-projection of the
  * non-local cell, :282-290 the two adds and the aggregation layer):
  *   out = relu( ( after + relu(skip_max ws + bs) + relu(att wb + bb) ) wagg + bagg )

@@ -30,6 +30,7 @@ SYMBOLS = [
     "pasnl_modelnet_fps_cap", "pasnl_modelnet_fps", "pasnl_modelnet_normalize", "pasnl_modelnet_batch", "pasnl_modelnet_augment", "pasnl_modelnet_noise", "pasnl_cls_vote", "pasnl_cls_tally",
     "pasnl_cls_tail_group_all", "pasnl_cls_nl_cell_input", "pasnl_cls_nl_cell_input_grad_workspace_bytes", "pasnl_cls_nl_cell_input_grad", "pasnl_cls_nl_attention_grad_workspace_bytes", "pasnl_cls_nl_attention_grad",
     "pasnl_cls_as_attention_grad", "pasnl_cls_as_attention_qkv_grad", "pasnl_cls_as_reweight_grad", "pasnl_cls_as_reweight_x_grad", "pasnl_cls_as_gather_grad_workspace_bytes", "pasnl_cls_as_gather_grad",
+    "pasnl_cls_sa_local_cell_grad_workspace_bytes", "pasnl_cls_sa_local_cell_grad", "pasnl_cls_sa_group_grad_workspace_bytes", "pasnl_cls_sa_group_grad",
     "pasnl_block_key_capacity", "pasnl_block_crop_stats", "pasnl_block_grid_count", "pasnl_block_fill", "pasnl_block_gather", "pasnl_block_normalize", "pasnl_block_score_workspace_bytes", "pasnl_block_score", "pasnl_block_train_batch", "pasnl_block_train_score",
     "pasnl_kblock_crop_stats", "pasnl_kblock_grid_count", "pasnl_kblock_fill", "pasnl_kblock_gather", "pasnl_kblock_rotate",
     "pasnl_grad_workspace_bytes", "pasnl_gather_point_grad_det", "pasnl_group_point_grad_det", "pasnl_three_interpolate_grad_det",
@@ -76,6 +77,8 @@ def lib():
         _lib.pasnl_cls_nl_attention_grad_workspace_bytes.restype = ctypes.c_size_t
         _lib.pasnl_cls_nl_cell_input_grad_workspace_bytes.restype = ctypes.c_size_t
         _lib.pasnl_cls_as_gather_grad_workspace_bytes.restype = ctypes.c_size_t
+        _lib.pasnl_cls_sa_local_cell_grad_workspace_bytes.restype = ctypes.c_size_t
+        _lib.pasnl_cls_sa_group_grad_workspace_bytes.restype = ctypes.c_size_t
         _lib.pasnl_window_hist_bytes.restype = ctypes.c_size_t
         _lib.pasnl_kwindow_hist_bytes.restype = ctypes.c_size_t
         _lib.pasnl_block_score_workspace_bytes.restype = ctypes.c_size_t

@@ -72,11 +72,76 @@ def grouping(feature, K, src_xyz, q_xyz, use_xyz=True, use_knn=True, radius=0.2)
     return grouped_xyz, grouped_feature, point_indices
 
 
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _grad_entry_supported(symbol, *dims):
+    """Whether a *_grad entry point takes these dimensions, asked of the entry itself with every pointer NULL: its header fixes the
+    order PASNL_EINVAL, PASNL_EUNSUPPORTED, (empty), PASNL_ENULL, all answered on the host before anything is enqueued."""
+    null = ctypes.c_void_p(0)
+    nptr = {"pasnl_cls_sa_group_grad": 10, "pasnl_cls_sa_local_cell_grad": 16}[symbol]  # pointers up to the workspace
+    code = getattr(_hip.lib(), symbol)(*dims, *([null] * nptr), ctypes.c_size_t(0), null)
+    if code == -1:
+        _hip.check(code, symbol)
+    return code != -5
+
+
+class _SAGroup(torch.autograd.Function):
+    """sa_group with the deterministic backward (pasnl_cls_sa_group_grad): saves the four inputs only; the maxima's masks are
+    recomputed from them."""
+
+    @staticmethod
+    def forward(ctx, xyz, feature, idx, new_xyz):
+        xyz, feature, idx, new_xyz = xyz.contiguous(), feature.contiguous(), idx.contiguous(), new_xyz.contiguous()
+        ctx.save_for_backward(xyz, feature, idx, new_xyz)
+        ctx.set_materialize_grads(False)
+        return _sa_group_forward(xyz, feature, idx, new_xyz)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_new_point, grad_skip):
+        xyz, feature, idx, new_xyz = ctx.saved_tensors
+        b, n, c = feature.shape
+        _, m, k = idx.shape
+        dev = idx.device
+        if grad_new_point is None and grad_skip is None:
+            return None, None, None, None
+        gnp = grad_new_point.contiguous() if grad_new_point is not None else None
+        gsk = grad_skip.contiguous() if grad_skip is not None else None
+        need = ctx.needs_input_grad
+        grad_xyz = torch.empty((b, n, 3), dtype=torch.float32, device=dev) if need[0] else None
+        grad_feature = torch.empty((b, n, c), dtype=torch.float32, device=dev) if need[1] else None
+        grad_new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if need[3] else None
+        nbytes = int(_hip.lib().pasnl_cls_sa_group_grad_workspace_bytes(b, n, c, m, k)) if (need[0] or need[1]) else 0
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        _hip.launch("pasnl_cls_sa_group_grad", "sa_group_grad", b, n, c, m, k, _hip.ptr(xyz), _hip.ptr(feature), _hip.ptr(idx),
+                    _hip.ptr(new_xyz), _hip.ptr(gnp), _hip.ptr(gsk), _hip.ptr(grad_xyz), _hip.ptr(grad_feature),
+                    _hip.ptr(grad_new_xyz), _hip.ptr(ws), ctypes.c_size_t(nbytes))
+        return grad_xyz, grad_feature, None, grad_new_xyz
+
+
 def sa_group(xyz, feature, idx, new_xyz):
     """Fused grouping of one set-abstraction layer (pointasnl_util.py:63-74, 248-249, 258):
         new_point[b,j,s,:] = [xyz[i]-new_xyz[j] | xyz[i] | feature[i]],  i = idx[b,j,s];   skip = max_s new_point
     One kernel instead of two gathers, two concats, a subtraction and a reduce_max.
-    -> new_point (B,P,K,6+C), skip (B,P,6+C)"""
+    -> new_point (B,P,K,6+C), skip (B,P,6+C)
+    Differentiable in xyz, feature and new_xyz (csrc/sa_grad.hip: the skip maximum's gradient is shared among equal elements, as
+    TensorFlow's reduce_max does; ordered sums, no fp atomics).  Beyond the backward's limits (N > 38400) a call that needs a
+    gradient composes group_point, cat and amax, which torch differentiates.  With no gradient needed -- inference, captured
+    graphs -- this is the plain launch."""
+    if _needs_grad(xyz, feature, new_xyz):
+        b, n, c = feature.shape
+        _, p, k = idx.shape
+        if _grad_entry_supported("pasnl_cls_sa_group_grad", b, n, c, p, k):
+            return _SAGroup.apply(xyz, feature, idx, new_xyz)
+        grouped_xyz = tf_grouping.group_point(xyz, idx)
+        new_point = torch.cat([grouped_xyz - new_xyz.unsqueeze(2), grouped_xyz, tf_grouping.group_point(feature, idx)], dim=-1)
+        return new_point, new_point.amax(dim=2)
+    return _sa_group_forward(xyz, feature, idx, new_xyz)
+
+
+def _sa_group_forward(xyz, feature, idx, new_xyz):
     b, n, c = feature.shape
     _, p, k = idx.shape
     xyz, feature, idx, new_xyz = xyz.contiguous(), feature.contiguous(), idx.contiguous(), new_xyz.contiguous()
@@ -114,24 +179,89 @@ def _local_cell_supported(w, mlp, nsample):
     return len(mlp) == 2 and mlp[0] in (32, 64, 128) + wide  # one convolution only (the *_2 layers of pointasnl_sem_seg_res.py)
 
 
-def sa_local_cell(new_point, mlp, is_training, bn_decay, weight_decay, bn):
-    """Fused local cell (pointasnl_util.py:264-274): conv0 -> conv1 on the grouped points, the weight net on the
-    centred coordinates, and H2^T . G, in one MFMA kernel.  (B,P,K,6+C) -> (B,P,mlp[1],32) = the input of after_conv.
-    The variables are the same ones the op-by-op chain would create (scopes conv0, conv1, weight_net/wconv0)."""
+class _SALocalCell(torch.autograd.Function):
+    """sa_local_cell_w with the fused deterministic backward (pasnl_cls_sa_local_cell_grad): saves the seven inputs only; H1, H2
+    and G are recomputed."""
+
+    @staticmethod
+    def forward(ctx, new_point, w0, b0, w1, b1, ww, bw):
+        args = tuple(t.contiguous() for t in (new_point, w0, b0, w1, b1, ww, bw))
+        ctx.save_for_backward(*args)
+        return _sa_local_cell_forward(*args)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, w0, b0, w1, b1, ww, bw = ctx.saved_tensors
+        b, p, k, w = x.shape
+        c1, c2 = w0.shape[1], w1.shape[1]
+        grad_out = grad_out.contiguous()
+        grads = [torch.empty_like(t) if need else None for t, need in zip((x, w0, b0, w1, b1, ww, bw), ctx.needs_input_grad)]
+        nbytes = int(_hip.lib().pasnl_cls_sa_local_cell_grad_workspace_bytes(b * p, w, c1, c2)) if any(ctx.needs_input_grad[1:]) else 0
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=x.device)
+        _hip.launch("pasnl_cls_sa_local_cell_grad", "sa_local_cell_grad", b * p, k, w, c1, c2, _hip.ptr(x), _hip.ptr(w0), _hip.ptr(b0),
+                    _hip.ptr(w1), _hip.ptr(b1), _hip.ptr(ww), _hip.ptr(bw), _hip.ptr(grad_out), *[_hip.ptr(g) for g in grads],
+                    _hip.ptr(ws), ctypes.c_size_t(nbytes))
+        return tuple(grads)
+
+
+def sa_local_cell_w(new_point, w0, b0, w1, b1, ww, bw):
+    """The local cell over explicit (BN-folded) weights: new_point (B,P,K,W), w0 (W,c1), b0 (c1), w1 (c1,c2), b1 (c2), ww (3,32),
+    bw (32) -> (B,P,c2,32) = H2^T . G with H1 = relu(X w0 + b0), H2 = relu(H1 w1 + b1), G = relu(X[..., :3] ww + bw).
+    Differentiable in all seven (csrc/sa_grad.hip: one MFMA kernel that recomputes H1, H2 and G, the weight gradients through
+    ordered partial sums; c1 = c2 in {32, 64}, the row widths include/pasnl.h lists).  Outside that set a call that needs a
+    gradient runs the op-by-op chain, which torch differentiates.  With no gradient needed this is the plain launch."""
+    if _needs_grad(new_point, w0, b0, w1, b1, ww, bw):
+        b, p, k, w = new_point.shape
+        if _grad_entry_supported("pasnl_cls_sa_local_cell_grad", b * p, k, w, int(w0.shape[1]), int(w1.shape[1])):
+            return _SALocalCell.apply(new_point, w0, b0, w1, b1, ww, bw)
+        h2 = torch.relu(torch.relu(new_point @ w0 + b0) @ w1 + b1)
+        return h2.transpose(2, 3) @ torch.relu(new_point[..., 0:3] @ ww + bw)
+    return _sa_local_cell_forward(new_point, w0, b0, w1, b1, ww, bw)
+
+
+def _sa_local_cell_forward(new_point, w0, b0, w1, b1, ww, bw):
     b, p, k, w = new_point.shape
-    c1, c2 = mlp[0], mlp[1]
-    st = tf_util.store()
-    with tf_util.variable_scope('conv0'):
-        w0, b0 = st.layer(w, c1, bn, weight_decay)
-    with tf_util.variable_scope('conv1'):
-        w1, b1 = st.layer(c1, c2, bn, weight_decay)
-    with tf_util.variable_scope('weight_net'), tf_util.variable_scope('wconv0'):
-        ww, bw = st.layer(3, 32, True, weight_decay)
+    c1, c2 = w0.shape[1], w1.shape[1]
     new_point = new_point.contiguous()
     out = torch.empty((b, p, c2, 32), dtype=torch.float32, device=new_point.device)
     _hip.launch("pasnl_sa_local_cell", "sa_local_cell", b * p, k, w, c1, c2, _hip.ptr(new_point), _hip.ptr(w0), _hip.ptr(b0),
                 _hip.ptr(w1), _hip.ptr(b1), _hip.ptr(ww), _hip.ptr(bw), _hip.ptr(out))
     return out
+
+
+def _layer_uncached(st, cin, cout, bn, weight_decay):
+    """st.layer at the current scope.  Where gradients are enabled and a variable of the layer requires one, the pair is folded
+    for this call and stays out of the store's cache: a cached fold that carries a graph would be walked again after its
+    backward has run, and one cached without a graph would cut the variables off."""
+    key = st.path("")
+    names = [key + leaf for leaf in ("weights", "biases", "bn/gamma", "bn/beta")]
+    if not (torch.is_grad_enabled() and any(st.vars[n].requires_grad for n in names if n in st.vars)):
+        return st.layer(cin, cout, bn, weight_decay)
+    cached = st._folded.pop(key, None)
+    try:
+        return st.layer(cin, cout, bn, weight_decay)
+    finally:
+        st._folded.pop(key, None)
+        if cached is not None and not any(t.requires_grad for t in cached):
+            st._folded[key] = cached
+
+
+def sa_local_cell(new_point, mlp, is_training, bn_decay, weight_decay, bn):
+    """Fused local cell (pointasnl_util.py:264-274): conv0 -> conv1 on the grouped points, the weight net on the
+    centred coordinates, and H2^T . G, in one MFMA kernel.  (B,P,K,6+C) -> (B,P,mlp[1],32) = the input of after_conv.
+    The variables are the same ones the op-by-op chain would create (scopes conv0, conv1, weight_net/wconv0).  The batch-norm
+    fold is torch's, so with sa_local_cell_w's backward the gradients reach weights, biases, gamma and beta."""
+    b, p, k, w = new_point.shape
+    c1, c2 = mlp[0], mlp[1]
+    st = tf_util.store()
+    with tf_util.variable_scope('conv0'):
+        w0, b0 = _layer_uncached(st, w, c1, bn, weight_decay)
+    with tf_util.variable_scope('conv1'):
+        w1, b1 = _layer_uncached(st, c1, c2, bn, weight_decay)
+    with tf_util.variable_scope('weight_net'), tf_util.variable_scope('wconv0'):
+        ww, bw = _layer_uncached(st, 3, 32, True, weight_decay)
+    return sa_local_cell_w(new_point, w0, b0, w1, b1, ww, bw)
 
 
 SA_CELL16 = True  # the 16-channel first layer on its own 16x16x4 kernel (False: zero-padded on the 32-channel kernel, A/B)
@@ -289,10 +419,6 @@ def weight_net_hidden(xyz, hidden_units, scope, is_training, bn_decay=None, weig
                                  is_training=is_training, activation_fn=activation_fn, scope='wconv%d' % (i),
                                  bn_decay=bn_decay, weight_decay=weight_decay)
     return net
-
-
-def _needs_grad(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
 
 
 class _ASAttention(torch.autograd.Function):
@@ -1102,6 +1228,13 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         new_xyz, _, idx = _resolved(search) if search is not None else sa_search(xyz, feature, npoint, nsample, use_knn, radius)
         new_feature = feature  # npoint == ndataset (:237-239); otherwise AdaptiveSampling defines it below (:246-247)
         nl_channel = mlp[-1]
+        # A gradient is asked for (gradients enabled and xyz, feature or a variable of the layer requires one): the differentiable
+        # route -- sa_group, sa_local_cell (or the torch chain), the op-by-op tail -- instead of the raw launches below, whose
+        # results carry no grad_fn.  With nothing requiring a gradient the dispatch and its bits are unchanged.
+        st_path = tf_util.store().path("")
+        diff = not is_training and torch.is_grad_enabled() and (
+            xyz.requires_grad or feature.requires_grad
+            or any(v.requires_grad for name, v in tf_util.store().vars.items() if name.startswith(st_path)))
 
         # ---- adaptive sampling (:244-247)
         fused = _local_cell_supported(6 + num_channel, mlp, nsample)
@@ -1119,9 +1252,13 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
             # the fused cell finds its centres in its own tiles and writes new_xyz / new_feature itself: no gather launch
             # between the search and the cell (pasnl_sa_cell_centre0)
             # (rows wider than 128 channels: only the wide kernels -- mlp[0] = 256 / 512 -- write the neighbour-0 row themselves)
-            centre0 = (CENTRE0 and fused and SA_CELL_GATHER and npoint <= num_points
+            centre0 = (not diff and CENTRE0 and fused and SA_CELL_GATHER and npoint <= num_points
                        and (num_channel <= 128 or (SA_CELL_WIDE and mlp[0] in (256, 512) and nsample == 32)))
-            if not centre0:
+            if diff:
+                idx0 = idx[:, :, 0].contiguous()  # (group_point has a backward; pasnl_take_neighbor0 is a raw launch)
+                new_xyz = _gather_rows(xyz, idx0)
+                new_feature = torch.cat([new_xyz, _gather_rows(feature, idx0)], dim=-1)
+            elif not centre0:
                 new_xyz, new_feature = take0()
         elif num_points != npoint and AS_FUSED and as_neighbor <= 16:
             tf_util._require_inference(is_training)
@@ -1138,7 +1275,7 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         if after_sampling is not None and not centre0:
             after_sampling(new_xyz)  # the sampled (and shifted) coordinates are final: the caller may start the next search
         new_point = None
-        if fused and SA_CELL_GATHER:
+        if fused and SA_CELL_GATHER and not diff:
             # grouping + skip max + local cell: one MFMA kernel reading the tables in place
             tf_util._require_inference(is_training)
             # (the table pays where every source point is gathered many times; both centre forms take the same route)
@@ -1184,7 +1321,7 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         c_out = mlp[-1]
         # (layers with few groups -- the deep, wide ones: 512 rows x 512 channels -- are 16 workgroups of dependent MFMA
         # chains fed from L2; there the three small vendor GEMMs are faster: measured 101 vs ~45 us)
-        if SA_TAIL_FUSED and c_out % 32 == 0 and c_out <= 512 and batch_size * npoint >= SA_TAIL_MIN_ROWS:
+        if SA_TAIL_FUSED and not diff and c_out % 32 == 0 and c_out <= 512 and batch_size * npoint >= SA_TAIL_MIN_ROWS:
             # skip convolution + back-projection of the non-local cell + both adds + aggregation: ONE kernel behind the
             # after_conv GEMM (pasnl_sa_tail) instead of three small GEMMs and two element-wise passes
             tf_util._require_inference(is_training)
