@@ -376,6 +376,20 @@ int pasnl_cls_tail_group_all(int b, int n, int w, int cb, int c, const float* af
                              float* out, float* pooled, long pooled_stride, void* workspace, size_t workspace_bytes,
                              pasnl_stream_t stream);
 
+/* The classifier's layer 2 tail and the first two convolutions of its layer3_2 group-all module in ONE launch
+ * (csrc/mlp_pool.hip): pasnl_sa_tail_packed(b * n rows, ...) with the same bits in `out`, then
+ * h2 (b*n,c2) = relu(relu([0 | new_xyz | out] w0 + b0) w1 + b1) for the module's third convolution; the (b*n, c+4) table and
+ * the (b*n,c1) activations stay in the workgroup's LDS.  The two convolutions are an fp32 fmaf chain in ascending k (1e-5 of
+ * the output scale against fp64: the contract of pasnl_mlp3_max_pool; not the bits of a vendor GEMM).  Arguments as for
+ * pasnl_cls_tail_group_all; w0 (c+4,c1), w1 (c1,c2) packed by pasnl_mlp3_pack_weights.  Covered: w = 134, cb = 64,
+ * c = c1 = 256, c2 = 512 -- anything else is PASNL_EUNSUPPORTED before any launch.  out (b*n,c) and h2 (b*n,c2) are fully
+ * written; h2_bytes: the size of the buffer at h2, at least b*n*c2*sizeof(float) (PASNL_EWORKSPACE otherwise). */
+int pasnl_cls_tail_mlp2(int b, int n, int w, int cb, int c, const float* after, const float* skip_max, const float* att,
+                        const float* ws_packed, const float* bs, const float* wb_packed, const float* bb,
+                        const float* wagg_packed, const float* bagg, const float* new_xyz, int c1, int c2, const float* w0,
+                        const float* b0, const float* w1, const float* b1, float* out, float* h2, size_t h2_bytes,
+                        pasnl_stream_t stream);
+
 /* ------------------------------------------------------------------ fp32-grade products on the bf16 matrix pipe (csrc/dense_bf16x3.hip)
  * An explicit MODE (the Python side's tf_util.DENSE_BF16X3; off by default, never used for the headline benchmark):
  * out (rows,n) = act(x (rows,kdim; row stride lda) . w + bias) for the long GEMMs behind tf_util.conv2d over a flattened

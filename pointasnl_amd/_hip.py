@@ -28,7 +28,7 @@ SYMBOLS = [
     "pasnl_window_noise", "pasnl_window_bounds", "pasnl_window_hist_bytes", "pasnl_window_count", "pasnl_window_fill", "pasnl_window_gather", "pasnl_window_vote", "pasnl_window_pool_labels",
     "pasnl_kwindow_hist_bytes", "pasnl_kwindow_count", "pasnl_kwindow_fill", "pasnl_kwindow_gather",
     "pasnl_modelnet_fps_cap", "pasnl_modelnet_fps", "pasnl_modelnet_normalize", "pasnl_modelnet_batch", "pasnl_modelnet_augment", "pasnl_modelnet_noise", "pasnl_cls_vote", "pasnl_cls_tally",
-    "pasnl_cls_tail_group_all", "pasnl_cls_nl_cell_input", "pasnl_cls_nl_cell_input_grad_workspace_bytes", "pasnl_cls_nl_cell_input_grad", "pasnl_cls_nl_attention_grad_workspace_bytes", "pasnl_cls_nl_attention_grad",
+    "pasnl_cls_tail_group_all", "pasnl_cls_tail_mlp2", "pasnl_cls_nl_cell_input", "pasnl_cls_nl_cell_input_grad_workspace_bytes", "pasnl_cls_nl_cell_input_grad", "pasnl_cls_nl_attention_grad_workspace_bytes", "pasnl_cls_nl_attention_grad",
     "pasnl_cls_as_attention_grad", "pasnl_cls_as_attention_qkv_grad", "pasnl_cls_as_reweight_grad", "pasnl_cls_as_reweight_x_grad", "pasnl_cls_as_gather_grad_workspace_bytes", "pasnl_cls_as_gather_grad",
     "pasnl_cls_sa_local_cell_grad_workspace_bytes", "pasnl_cls_sa_local_cell_grad", "pasnl_cls_sa_group_grad_workspace_bytes", "pasnl_cls_sa_group_grad",
     "pasnl_block_key_capacity", "pasnl_block_crop_stats", "pasnl_block_grid_count", "pasnl_block_fill", "pasnl_block_gather", "pasnl_block_normalize", "pasnl_block_score_workspace_bytes", "pasnl_block_score", "pasnl_block_train_batch", "pasnl_block_train_score",

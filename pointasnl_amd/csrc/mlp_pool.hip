@@ -20,7 +20,8 @@
 //
 // tail_group_all_kernel (pasnl_cls_tail_group_all) is layer3_1's form of the same kernel with the classifier's layer 1 tail in
 // front of it: the tile's X rows are not read from a table but computed in place from the tail's inputs (mlp3_tile is the part
-// the two kernels share; the tail's products are sa_tail.hpp's, shared with cells.hip).
+// the two kernels share; the tail's products are sa_tail.hpp's, shared with cells.hip).  tail_mlp2_kernel (pasnl_cls_tail_mlp2)
+// is layer 2's: its tail and the first two convolutions of layer3_2, whose third stays a vendor GEMM (see there).
 #include "common.hpp"
 #include "sa_tail.hpp"
 
@@ -88,7 +89,7 @@ __device__ __forceinline__ void mp_mm(const float* xrow, int rbstride, int NBT, 
 // one convolution of the tile: out[row][channel] = relu(in . W + bias), blocks of 32 channels dealt to the waves round robin
 template <int WOUT, int RB>
 __device__ __forceinline__ void mp_layer(const float* in, int pin, int K, const float* __restrict__ W, const float* __restrict__ bias,
-                                         float* out, int pout, int wave, int ql, int h) {
+                                         float* out, int pout, int wave, int ql, int h, int rows = 32 * RB) {
   constexpr int NW = 8, BLOCKS = WOUT / 32, NB = BLOCKS >= NW ? BLOCKS / NW : 1;
   if constexpr (BLOCKS * RB == NW && RB > 1) {
     // fewer blocks than waves (layer 0 of the narrower module): the tile's row blocks go to different waves instead of
@@ -116,7 +117,9 @@ __device__ __forceinline__ void mp_layer(const float* in, int pin, int K, const 
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) out[(rb * 32 + mp_kappa(r, h)) * pout + ch] = fmaxf(acc[rb][i][r] + bb, 0.f);
+      for (int r = 0; r < 16; ++r)
+        if (rb * 32 + mp_kappa(r, h) < rows)  // (rows: the default keeps every row -- the tile is LDS; a tile stored to memory ends with its cloud)
+          out[(rb * 32 + mp_kappa(r, h)) * pout + ch] = fmaxf(acc[rb][i][r] + bb, 0.f);
   }
 }
 
@@ -299,6 +302,123 @@ __global__ __launch_bounds__(512) void tail_group_all_kernel(int n, const float*
   mlp3_tile<TG_C, TG_C2, TG_C3, 2>(A, pa, Bf, TG_K0, w0, b0, w1, b1, w2, b2, partial + ((size_t)cloud * gridDim.x + tile) * TG_C3, wave, l32, h);
 }
 
+// ---- The classifier's layer 2 tail (sa_tail_kernel<8>, w = 134 skip columns, cb = 64, C = 256) and the first two convolutions
+// of layer3_2 (260 -> 256 -> 512) in one launch (pasnl_cls_tail_mlp2).  As three launches -- the tail and two vendor GEMMs of
+// 1.1 and 2.1 GFLOP -- each is a single wave of 256 workgroups whose time is one workgroup's chain of round trips, and `out`,
+// the [0 | xyz | out] table and H1 go out to memory and come back in between.  Here a workgroup of eight waves owns a tile of 32
+// rows of one cloud: the tail as in sa_tail_kernel<8> (wave = channel block, the products are tail_product's: the bits of the
+// separate launch), stage 2's D tile straight into the tile's X rows [0 | xyz | O | zeros to 272] in LDS, `out` stored from
+// there, then conv0 (X -> H1, LDS) and conv1 (H1 -> H2, stored with ReLU for the third convolution, which stays the vendor's
+// GEMM -- at 8192 rows its 8.6 GFLOP ran faster there than in mlp3_pool_kernel -- followed by the pooling pass).
+// LDS: X [32][273], behind it the tail's tiles V^T [256][33], S^T [160][33], N^T [64][33], which H1 [32][257] reuses.
+constexpr int T2_C = 256, T2_W = 134, T2_CB = 64, T2_K0 = T2_C + 4, T2_C1 = 256, T2_C2 = 512, T2_TR = 32;
+constexpr int T2_K0P = (T2_K0 + 15) & ~15;
+constexpr int T2_PA = T2_K0P | 1;
+constexpr int T2_WP = (T2_W + 2 * TAIL_KS - 1) & ~(2 * TAIL_KS - 1);
+constexpr int T2_TAIL_FLOATS = (T2_C + T2_WP + T2_CB) * 33;
+constexpr int T2_H1_FLOATS = T2_TR * (T2_C1 + 1);
+constexpr size_t T2_LDS_BYTES = ((size_t)T2_TR * T2_PA + (T2_TAIL_FLOATS > T2_H1_FLOATS ? T2_TAIL_FLOATS : T2_H1_FLOATS)) * sizeof(float);
+static_assert(T2_LDS_BYTES <= LDS_MAX_BYTES, "X rows + the tail's tiles fit one workgroup's LDS");
+static_assert(T2_C == 8 * 32 && T2_C1 == 8 * 32 && T2_C2 % 256 == 0 && T2_C % 64 == 0 && T2_CB == 64 && T2_WP <= 192 && T2_K0P - T2_K0 <= 60,
+              "one channel block per wave; the staging's segment counts");
+
+__global__ __launch_bounds__(512) void tail_mlp2_kernel(int n, const float* __restrict__ after, const float* __restrict__ S,
+                                                        const float* __restrict__ N, const float* __restrict__ Ws,
+                                                        const float* __restrict__ bs, const float* __restrict__ Wb,
+                                                        const float* __restrict__ bb, const float* __restrict__ Wagg,
+                                                        const float* __restrict__ bagg, const float* __restrict__ xyz3,
+                                                        const float* __restrict__ w0, const float* __restrict__ b0,
+                                                        const float* __restrict__ w1, const float* __restrict__ b1,
+                                                        float* __restrict__ out, float* __restrict__ h2) {
+  constexpr int C = T2_C, pa = T2_PA, RPW = T2_TR / 8, SA = C / 64, SS = (T2_WP + 63) / 64;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* A = reinterpret_cast<float*>(smem);  // [32][pa]: X = [0 | xyz | O | zeros to 272]
+  float* Bf = A + T2_TR * pa;                 // the tail's tiles, then H1 [32][C1 + 1]
+  float* vt = Bf;                             // [C][33]   V^T
+  float* st = vt + C * 33;                    // [WP][33]  S^T, zero beyond w
+  float* nt_ = st + T2_WP * 33;               // [CB][33]  N^T
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l32 = lane & 31;
+  const int tile = blockIdx.x, cloud = blockIdx.y;
+  const long cloud0 = (long)cloud * n;
+  // ---- the tile's rows, every request before the first write (one round trip); a row past the cloud repeats its last point
+  {
+    float va[SA][RPW], vs[SS][RPW], vn[RPW], cx[RPW];
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      const long row = cloud0 + min(tile * T2_TR + wave * RPW + i, n - 1);
+#pragma unroll
+      for (int s = 0; s < SA; ++s) va[s][i] = after[row * C + s * 64 + lane];
+#pragma unroll
+      for (int s = 0; s < SS; ++s) vs[s][i] = S[row * T2_W + min(s * 64 + lane, T2_W - 1)];
+      vn[i] = N[row * T2_CB + lane];
+      cx[i] = xyz3[row * 3 + max(min(lane, 3) - 1, 0)];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      const int r = wave * RPW + i;
+#pragma unroll
+      for (int s = 0; s < SA; ++s) vt[(s * 64 + lane) * 33 + r] = va[s][i];
+#pragma unroll
+      for (int s = 0; s < SS; ++s) {
+        const int c = s * 64 + lane;
+        if (c < T2_WP) st[c * 33 + r] = c < T2_W ? vs[s][i] : 0.f;
+      }
+      nt_[lane * 33 + r] = vn[i];
+      float* xr = A + r * pa;
+      if (lane < 4) xr[lane] = lane ? cx[i] : 0.f;
+      else if (lane < 4 + T2_K0P - T2_K0) xr[T2_K0 + lane - 4] = 0.f;  // conv0 contracts to a multiple of 16
+    }
+  }
+  __syncthreads();
+  const int cbase = wave * 32;
+  // ---- tail stage 1: V^T += relu(Ws^T S^T + bs) + relu(Wb^T N^T + bb)
+  {
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = bs[cbase + kappa(i, h)];
+    acc = tail_product(TailW<true>{Ws, C, T2_W, h, cbase + l32}, st, l32, acc);
+    f32x16 v;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = fmaxf(acc[i], 0.f);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = bb[cbase + kappa(i, h)];
+    acc = tail_product(TailW<true>{Wb, C, T2_CB, h, cbase + l32}, nt_, l32, acc);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] += fmaxf(acc[i], 0.f);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float* cell = vt + (cbase + kappa(i, h)) * 33 + l32;
+      *cell = *cell + v[i];
+    }
+  }
+  __syncthreads();
+  // ---- tail stage 2: O^T = relu(Wagg^T V^T + bagg), the lane's 16 channels of row l32 straight into the tile's X row
+  {
+    f32x16 o;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[i] = bagg[cbase + kappa(i, h)];
+    o = tail_product(TailW<true>{Wagg, C, C, h, cbase + l32}, vt, l32, o);
+    float* xr = A + l32 * pa + 4 + cbase;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) xr[kappa(i, h)] = fmaxf(o[i], 0.f);
+  }
+  __syncthreads();  // X is complete, and every wave has read V^T: H1 may overwrite the tail's tiles
+  // ---- the layer's output rows (256-byte pieces; the stores drain behind conv0's products)
+#pragma unroll
+  for (int i = 0; i < RPW; ++i) {
+    const int r = wave * RPW + i, row = tile * T2_TR + r;
+    if (row < n) {
+      float* o = out + (cloud0 + row) * C;
+#pragma unroll
+      for (int s = 0; s < SA; ++s) o[s * 64 + lane] = A[r * pa + 4 + s * 64 + lane];
+    }
+  }
+  mp_layer<T2_C1, 1>(A, pa, T2_K0, w0, b0, Bf, T2_C1 + 1, wave, l32, h);
+  __syncthreads();
+  mp_layer<T2_C2, 1>(Bf, T2_C1 + 1, T2_C1, w1, b1, h2 + (cloud0 + (long)tile * T2_TR) * T2_C2, T2_C2, wave, l32, h, n - tile * T2_TR);
+}
+
 // W (K, N) row-major -> P[bt][h][n][u] = W[16 bt + 2 u + h][n] (zero beyond K): one thread per 16-byte piece
 __global__ __launch_bounds__(256) void mlp3_pack_kernel(int K, int N, const float* __restrict__ W, float* __restrict__ P) {
   const long total = (long)((K + 15) >> 4) * 2 * N * 2;  // 16-byte pieces
@@ -401,4 +521,25 @@ extern "C" int pasnl_cls_tail_group_all(int b, int n, int w, int cb, int c, cons
     return PASNL_ELAUNCH;
   if (pasnl_launch_status() != PASNL_OK) return PASNL_ELAUNCH;
   return pasnl_max_pool_rows_strided(b, tiles, c3, static_cast<const float*>(workspace), pooled, pooled_stride, stream);
+}
+
+extern "C" int pasnl_cls_tail_mlp2(int b, int n, int w, int cb, int c, const float* after, const float* skip_max, const float* att,
+                                   const float* ws_packed, const float* bs, const float* wb_packed, const float* bb,
+                                   const float* wagg_packed, const float* bagg, const float* new_xyz, int c1, int c2, const float* w0,
+                                   const float* b0, const float* w1, const float* b1, float* out, float* h2, size_t h2_bytes,
+                                   pasnl_stream_t stream) {
+  PASNL_REQUIRE(b >= 0 && n > 0 && w > 0 && cb > 0 && c > 0 && c1 > 0 && c2 > 0, PASNL_EINVAL);
+  if (b == 0) return PASNL_OK;
+  PASNL_REQUIRE(after && skip_max && att && ws_packed && bs && wb_packed && bb && wagg_packed && bagg && new_xyz, PASNL_ENULL);
+  PASNL_REQUIRE(w0 && b0 && w1 && b1 && out && h2, PASNL_ENULL);
+  PASNL_REQUIRE(w == T2_W && cb == T2_CB && c == T2_C && c1 == T2_C1 && c2 == T2_C2, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(h2_bytes >= (size_t)b * n * c2 * sizeof(float), PASNL_EWORKSPACE);
+  PASNL_REQUIRE(b <= 65535, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE((reinterpret_cast<uintptr_t>(ws_packed) | reinterpret_cast<uintptr_t>(wb_packed) | reinterpret_cast<uintptr_t>(wagg_packed) |
+                 reinterpret_cast<uintptr_t>(w0) | reinterpret_cast<uintptr_t>(w1)) % 16 == 0,
+                PASNL_EUNSUPPORTED);  // (packed weights: read in 16-byte pieces)
+  if (launch(tail_mlp2_kernel, dim3((n + T2_TR - 1) / T2_TR, b), dim3(512), T2_LDS_BYTES, pasnl_hip_stream(stream), n, after, skip_max, att,
+             ws_packed, bs, wb_packed, bb, wagg_packed, bagg, new_xyz, w0, b0, w1, b1, out, h2) != PASNL_OK)
+    return PASNL_ELAUNCH;
+  return pasnl_launch_status();
 }

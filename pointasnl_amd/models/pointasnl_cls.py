@@ -48,6 +48,9 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     # 1.429 ms in every one of three alternated runs; EXPERIMENTS.md, "The non-local cell of a narrow level"): the cb-wide kernels
     # unless asked for
     nl_input_space = not adaptive_sample or pointasnl_util.NL_INPUT_SPACE == "always"
+    # layer 2's tail with layer3_2's first two convolutions (pasnl_cls_tail_mlp2): with adaptive sampling it was not measured,
+    # so there it runs only when asked for
+    fuse3_2 = not adaptive_sample or pointasnl_util.SA_TAIL_MLP2 == "always"
 
     # Set abstraction layers.  Layer 2's search (FPS + kNN) reads layer 1's sampled coordinates only, so it is forked onto
     # a side stream the moment those are final and runs beside layer 1's MFMA / GEMM work (pointasnl_util.Forked)
@@ -66,6 +69,7 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     l2_xyz, l2_points = PointASNLSetAbstraction(l1_xyz, l1_points, npoint=128, nsample=64, mlp=[128, 128, 256],
                                                 is_training=is_training, bn_decay=bn_decay, weight_decay=weight_decay,
                                                 scope='layer2', as_neighbor=as_neighbor[1], search=search2[0], xyz_concat=True,
+                                                group_all=dict(mlp=[256, 512, 1024], scope='layer3_2', pooled_out=net[:, :1024]) if fuse3_2 else None,
                                                 after_cell=before_head if fork_at == "cell2" else None,
                                                 before_after_conv=before_head if fork_at == "conv2" else None)
     end_points['l2_xyz'] = l1_xyz  # sic: the reference stores l1_xyz here (pointasnl_cls.py:38)
@@ -75,9 +79,10 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
         _, l3_points_res, _ = pointnet_sa_module(l1_xyz, l1_points, npoint=None, radius=None, nsample=None,
                                                  mlp=[128, 256, 512], mlp2=None, group_all=True, is_training=is_training,
                                                  bn_decay=bn_decay, scope='layer3_1', pooled_out=net[:, 1024:])
-    _, l3_points, _ = pointnet_sa_module(l2_xyz, l2_points, npoint=None, radius=None, nsample=None,
-                                         mlp=[256, 512, 1024], mlp2=None, group_all=True, is_training=is_training,
-                                         bn_decay=bn_decay, scope='layer3_2', pooled_out=net[:, :1024])
+    if getattr(l2_points, "group_all_pooled", None) is None:  # (else layer 2's tail ran layer3_2 as well: net[:, :1024] is written)
+        _, l3_points, _ = pointnet_sa_module(l2_xyz, l2_points, npoint=None, radius=None, nsample=None,
+                                             mlp=[256, 512, 1024], mlp2=None, group_all=True, is_training=is_training,
+                                             bn_decay=bn_decay, scope='layer3_2', pooled_out=net[:, :1024])
 
     # Fully connected layers
     net = tf_util.fully_connected(net, 512, bn=True, is_training=is_training, scope='fc1', bn_decay=bn_decay)

@@ -161,6 +161,9 @@ SA_CELL_PACKED = True    # the wide cells (one workgroup per group, weights from
 SA_TAIL_PACKED = True    # pasnl_sa_tail with its weights packed in operand order (16-byte weight loads)
 SA_TAIL_GROUP_ALL = True  # the classifier's layer 1: tail + the layer3_1 group_all module in one launch (pasnl_cls_tail_group_all) where it was
                           # measured faster -- without adaptive sampling; "always": with it too (0.5 % slower there); False = two launches (A/B)
+SA_TAIL_MLP2 = True      # the classifier's layer 2: tail + the first two convolutions of the layer3_2 group_all module in one launch
+                         # (pasnl_cls_tail_mlp2; fp32 MFMA instead of two vendor GEMMs: 1e-5 of scale, not their bits) -- without
+                         # adaptive sampling; "always": with it too (not measured there); False = today's launches and bits (A/B)
 SA_TAIL_FUSED = True     # skip conv + back-projection + adds + aggregation in one kernel (pasnl_sa_tail); False = op by op
 SA_CELL_GATHER = True    # grouping fused into the local cell (pasnl_sa_cell); False = pasnl_sa_group + pasnl_sa_local_cell
 SA_CELL_SINGLE = True     # mlp = [c, c] (one convolution, c = 32 / 64 / 128): no conv1 at all instead of an identity conv1 (False: A/B)
@@ -1221,6 +1224,15 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         # the module's variables are named by ITS scope path, not by this layer's: resolved out here
         with tf_util.variable_scope(group_all['scope']):
             ga_weights = pointnet_util.group_all_weights(group_all['mlp'], 3 + mlp[-1], 1, bn)
+    # layer 2's form (pasnl_cls_tail_mlp2: 134 skip columns, 64 attention channels, 256 -> [256, 512 | 1024]): the tail and the
+    # module's first two convolutions in one launch; its third convolution and the pooling pass follow with the module's own
+    # variables, so new_points carries `.group_all_pooled` here too
+    mlp2_weights = mlp2_scope = None
+    if (group_all is not None and SA_TAIL_MLP2 and SA_TAIL_FUSED and SA_TAIL_PACKED and NL and residual is None and not is_training
+            and mlp[-1] == 256 and tuple(group_all['mlp']) == (256, 512, 1024)):
+        with tf_util.variable_scope(group_all['scope']):
+            mlp2_weights = pointnet_util.group_all_weights(group_all['mlp'][:2], 3 + mlp[-1], 1, bn)
+            mlp2_scope = list(tf_util.store()._scope)
     with tf_util.variable_scope(scope):
         batch_size, num_points, num_channel = feature.shape
         # Farthest point sampling + neighbour search (the reference's sampling() / grouping(): pointasnl_util.py:236-242);
@@ -1368,6 +1380,23 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
                                     _hip.ptr(wsb), ctypes.c_size_t(wsb.numel()))
                         out.group_all_pooled = pooled
                         return new_xyz, out
+                    if mlp2_weights is not None and (int(w_in), int(cb)) == (134, 64) and new_xyz.shape[1] == npoint:
+                        # tail + the caller's group_all module up to its second convolution: one launch, no [0 | xyz | out]
+                        # table, no H1; then the module's third convolution (vendor GEMM) and the pooling pass
+                        new_xyz = new_xyz.contiguous()
+                        gmlp = group_all['mlp']
+                        h2 = torch.empty((batch_size, 1, npoint, gmlp[1]), dtype=torch.float32, device=xyz.device)
+                        try:
+                            _hip.launch("pasnl_cls_tail_mlp2", "sa_tail_mlp2", batch_size, npoint, int(w_in), int(cb), int(c_out),
+                                        *args[4:7], _hip.ptr(pk[0]), args[8], _hip.ptr(pk[1]), args[10], _hip.ptr(pk[2]), args[12],
+                                        _hip.ptr(new_xyz), gmlp[0], gmlp[1], *[_hip.ptr(t) for t in mlp2_weights], args[13],
+                                        _hip.ptr(h2), ctypes.c_size_t(h2.numel() * 4))
+                        except _hip.PasnlUnsupported:
+                            h2 = None  # today's launches below
+                        if h2 is not None:
+                            with tf_util.store().scope_at(mlp2_scope):
+                                out.group_all_pooled = pointnet_util.group_all_last(h2, gmlp[2], bn, group_all.get('pooled_out'))
+                            return new_xyz, out
                     if xyz_concat and XYZ_CONCAT:
                         new_xyz = new_xyz.contiguous()
                         cat = torch.empty((batch_size, npoint, 4 + c_out), dtype=torch.float32, device=xyz.device)

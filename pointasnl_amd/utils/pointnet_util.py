@@ -108,6 +108,15 @@ def group_all_workspace(b, n, c3, device):
     return bufs[-1]
 
 
+def group_all_last(h2, c3, bn, pooled_out=None):
+    """The end of a group_all module whose first two convolutions ran elsewhere (pasnl_cls_tail_mlp2): the third convolution
+    (scope conv2 at the current scope; the vendor GEMM) over h2 (B,1,n,c2) and the maximum over the points -> the (B, c3) view."""
+    x = tf_util.conv2d(h2, c3, [1, 1], padding='VALID', stride=[1, 1], bn=bn, is_training=False, scope='conv2')
+    out2d = group_all_pooled(pooled_out, h2.shape[0], c3, h2.device)
+    max_pool_points(x, out=out2d)
+    return out2d
+
+
 def group_all_mlp_max(new_points, mlp, bn, pooled_out=None):
     """The body of a group_all module (pointnet_util.py:123-137) in one launch (csrc/mlp_pool.hip): the three [1,1] convolutions
     of `mlp` (BN folded, ReLU) over all n points of every cloud and the maximum over the points.

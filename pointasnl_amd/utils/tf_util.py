@@ -46,6 +46,15 @@ class VariableStore:
         finally:
             self._scope.pop()
 
+    @contextlib.contextmanager
+    def scope_at(self, names):
+        """the scope stack replaced by `names`: another module's variables resolved from inside this module's scope"""
+        saved, self._scope = self._scope, list(names)
+        try:
+            yield
+        finally:
+            self._scope = saved
+
     def path(self, name):
         return "/".join(self._scope + [name])
 
