@@ -1,4 +1,4 @@
-// Backward of the AdaptiveSampling cell's three parts that are not GEMMs (cells.hip: as_attention_kernel, as_reweight_kernel,
+// Backward of the AdaptiveSampling cell's three parts that are not GEMMs (as_cell.hip: as_attention_kernel, as_reweight_kernel,
 // as_gather_*_kernel) for gfx950: pasnl_cls_as_attention_grad / _qkv_grad, pasnl_cls_as_reweight_grad / _x_grad and
 // pasnl_cls_as_gather_grad.  DESIGN.md 4.4 has the formulas and the resource figures.
 //
@@ -24,26 +24,9 @@
 // point, r[j,s] = [gx[0:3] + gx[3:6] - (s == 0 ? sum_t gx[j,t,0:3] : 0) | gx[6:]], and r is scattered by the ordered segmented
 // sums of grouping.hip (pasnl_group_point_grad_det): no second scatter, no fp atomics.
 #include <math.h>
-#include "common.hpp"
-#include "sa_tail.hpp"
+#include "as_core.hpp"
 
 namespace pasnl {
-
-typedef float asg_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int ASG_MAX = 16;  // neighbours per group (the 16 x 16 tile; cells.hip: AS_MAX)
-
-// a value combined over the 16 lanes of a row (lanes that share lane >> 4): four DPP exchanges, the same bits in every lane
-__device__ __forceinline__ float row16_max(float v) {
-#pragma unroll
-  for (int j = 1; j < 16; j <<= 1) v = fmaxf(v, __uint_as_float(shfl_xor_u32(__float_as_uint(v), j)));
-  return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-#pragma unroll
-  for (int j = 1; j < 16; j <<= 1) v += __uint_as_float(shfl_xor_u32(__float_as_uint(v), j));
-  return v;
-}
 
 // qs / kvs = row strides of q and kv in floats, gqs / gkvs those of grad_q and grad_kv (cb and 2cb for separate tensors; 3cb
 // for one [K | V | Q] tensor and its gradient); gout rows are cb floats
@@ -63,7 +46,7 @@ __global__ __launch_bounds__(256) void as_attention_grad_kernel(long groups, int
 
   if (grad_q != nullptr) {
     // ---- key-major: S^T[key = 4 grp + r][query = col], dP^T likewise; dQ^T[ch][query] += K^T . dS^T
-    asg_f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {0.f, 0.f, 0.f, 0.f};
+    f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < cb; c0 += 4) {
       const int c = c0 + grp;
       const bool okc = rowok && c < cb;
@@ -74,23 +57,7 @@ __global__ __launch_bounds__(256) void as_attention_grad_kernel(long groups, int
       S = __builtin_amdgcn_mfma_f32_16x16x4f32(kk, qq, S, 0, 0, 0);
       dP = __builtin_amdgcn_mfma_f32_16x16x4f32(vv, go, dP, 0, 0, 0);
     }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      S[r] = (4 * grp + r) < as ? S[r] : -INFINITY;
-      tmax = fmaxf(tmax, S[r]);
-    }
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
-    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));  // finite: key 0 exists
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      S[r] = fast_exp2(S[r] - tmax);
-      psum += S[r];
-    }
-    psum += __shfl_xor(psum, 16);
-    psum += __shfl_xor(psum, 32);
-    const float inv = 1.0f / psum;
+    const float inv = as_softmax_keys(S, as, grp);
     float delta = 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -105,7 +72,7 @@ __global__ __launch_bounds__(256) void as_attention_grad_kernel(long groups, int
       S[r] = (rowok && (4 * grp + r) < as) ? ds : 0.f;
     }
     for (int c0 = 0; c0 < cb; c0 += 16) {
-      asg_f32x4 O = {0.f, 0.f, 0.f, 0.f};
+      f32x4 O = {0.f, 0.f, 0.f, 0.f};
       const int ch = c0 + col;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -124,7 +91,7 @@ __global__ __launch_bounds__(256) void as_attention_grad_kernel(long groups, int
 
   if (grad_kv != nullptr) {
     // ---- query-major: S[query = 4 grp + r][key = col], dP likewise; dV^T[ch][key] += g^T . P, dK^T[ch][key] += Q^T . dS
-    asg_f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {0.f, 0.f, 0.f, 0.f};
+    f32x4 S = {0.f, 0.f, 0.f, 0.f}, dP = {0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < cb; c0 += 4) {
       const int c = c0 + grp;
       const bool okc = rowok && c < cb;
@@ -135,7 +102,7 @@ __global__ __launch_bounds__(256) void as_attention_grad_kernel(long groups, int
       S = __builtin_amdgcn_mfma_f32_16x16x4f32(qq, kk, S, 0, 0, 0);
       dP = __builtin_amdgcn_mfma_f32_16x16x4f32(go, vv, dP, 0, 0, 0);
     }
-    asg_f32x4 P, dS;
+    f32x4 P, dS;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float s = rowok ? S[r] : -INFINITY;
@@ -149,7 +116,7 @@ __global__ __launch_bounds__(256) void as_attention_grad_kernel(long groups, int
       dS[r] = valid ? pr * (dP[r] - dl) : 0.f;
     }
     for (int c0 = 0; c0 < cb; c0 += 16) {
-      asg_f32x4 dV = {0.f, 0.f, 0.f, 0.f}, dK = {0.f, 0.f, 0.f, 0.f};
+      f32x4 dV = {0.f, 0.f, 0.f, 0.f}, dK = {0.f, 0.f, 0.f, 0.f};
       const int ch = c0 + col;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -190,32 +157,23 @@ __global__ __launch_bounds__(256) void as_reweight_grad_kernel(long groups, int 
     const long g = e / w;
     const int o = (int)(e - g * w);
     const float* lg = logits + (size_t)g * as * w;
-    // softmax over the neighbours of column `column`, as the forward forms it
-    auto softmax_column = [&](int column, float (&v)[ASG_MAX]) {
-      float mx = -INFINITY;
+    // softmax over the neighbours of column `column`: the forward's, normalised as it normalises
+    auto softmax_column = [&](int column, float (&v)[AS_MAX]) {
 #pragma unroll
-      for (int k = 0; k < ASG_MAX; ++k) {
-        v[k] = k < as ? lg[(size_t)k * w + column] : -INFINITY;
-        mx = fmaxf(mx, v[k]);
-      }
-      float sum = 0.f;
+      for (int k = 0; k < AS_MAX; ++k) v[k] = k < as ? lg[(size_t)k * w + column] : -INFINITY;
+      const float sum = as_softmax_column(as, v);
 #pragma unroll
-      for (int k = 0; k < ASG_MAX; ++k) {
-        v[k] = k < as ? expf(v[k] - mx) : 0.f;
-        sum += v[k];
-      }
-#pragma unroll
-      for (int k = 0; k < ASG_MAX; ++k) v[k] = v[k] / sum;
+      for (int k = 0; k < AS_MAX; ++k) v[k] = v[k] / sum;
     };
-    float v[ASG_MAX];
+    float v[AS_MAX];
     softmax_column(o, v);
     const float gx0 = gnx[g * 3], gx1 = gnx[g * 3 + 1], gx2 = gnx[g * 3 + 2];
     const float gf = o > 0 ? gnf[(size_t)g * ch + (o - 1)] : 0.f;
     if (grad_logits != nullptr) {
-      float t[ASG_MAX];
+      float t[AS_MAX];
       float dot = 0.f;
 #pragma unroll
-      for (int k = 0; k < ASG_MAX; ++k) {
+      for (int k = 0; k < AS_MAX; ++k) {
         t[k] = 0.f;
         if (k < as) {
           if (o == 0) {
@@ -228,7 +186,7 @@ __global__ __launch_bounds__(256) void as_reweight_grad_kernel(long groups, int 
         }
       }
 #pragma unroll
-      for (int k = 0; k < ASG_MAX; ++k)
+      for (int k = 0; k < AS_MAX; ++k)
         if (k < as) grad_logits[((size_t)g * as + k) * w + o] = v[k] * (t[k] - dot);
     }
     if constexpr (XFORM) {
@@ -239,22 +197,22 @@ __global__ __launch_bounds__(256) void as_reweight_grad_kernel(long groups, int 
           p[0] = 0.f; p[1] = 0.f; p[2] = 0.f;
         }
       } else if (o <= 3) {  // the columns that serve as coordinates too: dF + dX
-        float v0[ASG_MAX];
+        float v0[AS_MAX];
         softmax_column(0, v0);
         const float gxd = o == 1 ? gx0 : o == 2 ? gx1 : gx2;
 #pragma unroll
-        for (int k = 0; k < ASG_MAX; ++k)
+        for (int k = 0; k < AS_MAX; ++k)
           if (k < as) grad_f[((size_t)g * as + k) * gfs + (o - 1)] = v[k] * gf + v0[k] * gxd;
       } else {
 #pragma unroll
-        for (int k = 0; k < ASG_MAX; ++k)
+        for (int k = 0; k < AS_MAX; ++k)
           if (k < as) grad_f[((size_t)g * as + k) * gfs + (o - 1)] = v[k] * gf;
       }
     } else {
       if (o == 0) {
         if (grad_x != nullptr) {
 #pragma unroll
-          for (int k = 0; k < ASG_MAX; ++k)
+          for (int k = 0; k < AS_MAX; ++k)
             if (k < as) {
               float* p = grad_x + ((size_t)g * nsample + k) * gxs;
               p[0] = v[k] * gx0; p[1] = v[k] * gx1; p[2] = v[k] * gx2;
@@ -266,7 +224,7 @@ __global__ __launch_bounds__(256) void as_reweight_grad_kernel(long groups, int 
         }
       } else if (grad_f != nullptr) {
 #pragma unroll
-        for (int k = 0; k < ASG_MAX; ++k)
+        for (int k = 0; k < AS_MAX; ++k)
           if (k < as) grad_f[((size_t)g * nsample + k) * gfs + (o - 1)] = v[k] * gf;
         for (int k = as; k < nsample; ++k) grad_f[((size_t)g * nsample + k) * gfs + (o - 1)] = 0.f;
       }
@@ -301,16 +259,10 @@ __global__ __launch_bounds__(256) void as_gather_fold_kernel(int c, int k, int a
   }
 }
 
-static unsigned asg_grid(long total) {
-  const long grid = (total + 255) / 256;
-  return (unsigned)(grid > 16384 ? 16384 : grid);
-}
-
 static int as_attention_grad_launch(int g, int as, int cb, int qs, int kvs, int gqs, int gkvs, const float* q, const float* kv,
                                     const float* gout, float* grad_q, float* grad_kv, hipStream_t st) {
-  const float qscale = LOG2E / sqrtf((float)cb), gscale = 1.0f / sqrtf((float)cb);
-  hipLaunchKernelGGL(as_attention_grad_kernel, dim3((unsigned)(((long)g + 3) / 4)), dim3(256), 0, st, (long)g, as, cb, qscale, gscale,
-                     qs, kvs, gqs, gkvs, q, kv, gout, grad_q, grad_kv);
+  hipLaunchKernelGGL(as_attention_grad_kernel, dim3((unsigned)(((long)g + 3) / 4)), dim3(256), 0, st, (long)g, as, cb, as_qscale(cb),
+                     1.0f / sqrtf((float)cb), qs, kvs, gqs, gkvs, q, kv, gout, grad_q, grad_kv);
   return pasnl_launch_status();
 }
 
@@ -321,7 +273,7 @@ using namespace pasnl;
 extern "C" int pasnl_cls_as_attention_grad(int g, int as, int cb, const float* q, const float* kv, const float* grad_out,
                                            float* grad_q, float* grad_kv, pasnl_stream_t stream) {
   PASNL_REQUIRE(g >= 0 && as > 0 && cb > 0, PASNL_EINVAL);
-  PASNL_REQUIRE(as <= ASG_MAX && cb <= 256, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(as <= AS_MAX && cb <= 256, PASNL_EUNSUPPORTED);
   if (g == 0) return PASNL_OK;
   PASNL_REQUIRE(q && kv && grad_out && (grad_q || grad_kv), PASNL_ENULL);
   return as_attention_grad_launch(g, as, cb, cb, 2 * cb, cb, 2 * cb, q, kv, grad_out, grad_q, grad_kv, pasnl_hip_stream(stream));
@@ -330,7 +282,7 @@ extern "C" int pasnl_cls_as_attention_grad(int g, int as, int cb, const float* q
 extern "C" int pasnl_cls_as_attention_qkv_grad(int g, int as, int cb, const float* kvq, const float* grad_out, float* grad_kvq,
                                                pasnl_stream_t stream) {
   PASNL_REQUIRE(g >= 0 && as > 0 && cb > 0, PASNL_EINVAL);
-  PASNL_REQUIRE(as <= ASG_MAX && cb <= 256, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(as <= AS_MAX && cb <= 256, PASNL_EUNSUPPORTED);
   if (g == 0) return PASNL_OK;
   PASNL_REQUIRE(kvq && grad_out && grad_kvq, PASNL_ENULL);
   return as_attention_grad_launch(g, as, cb, 3 * cb, 3 * cb, 3 * cb, 3 * cb, kvq + 2 * cb, kvq, grad_out, grad_kvq + 2 * cb, grad_kvq,
@@ -342,12 +294,12 @@ extern "C" int pasnl_cls_as_reweight_grad(int g, int as, int nsample, int ch, co
                                           float* grad_logits, float* grad_grouped_xyz, float* grad_grouped_feature,
                                           pasnl_stream_t stream) {
   PASNL_REQUIRE(g >= 0 && as > 0 && nsample >= as && ch > 0, PASNL_EINVAL);
-  PASNL_REQUIRE(as <= ASG_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(as <= AS_MAX, PASNL_EUNSUPPORTED);
   if (g == 0) return PASNL_OK;
   PASNL_REQUIRE(logits && grad_new_xyz && grad_new_feature && (grad_logits || grad_grouped_xyz || grad_grouped_feature),
                 PASNL_ENULL);
   PASNL_REQUIRE(grad_logits == nullptr || (grouped_xyz && grouped_feature), PASNL_ENULL);
-  hipLaunchKernelGGL(as_reweight_grad_kernel<false>, dim3(asg_grid((long)g * (1 + ch))), dim3(256), 0, pasnl_hip_stream(stream),
+  hipLaunchKernelGGL(as_reweight_grad_kernel<false>, dim3(as_grid((long)g * (1 + ch))), dim3(256), 0, pasnl_hip_stream(stream),
                      (long)g, as, nsample, ch, 3, ch, 3, ch, logits, grouped_xyz, grouped_feature, grad_new_xyz, grad_new_feature,
                      grad_logits, grad_grouped_xyz, grad_grouped_feature);
   return pasnl_launch_status();
@@ -357,13 +309,13 @@ extern "C" int pasnl_cls_as_reweight_x_grad(int g, int as, int ch, const float* 
                                             const float* grad_new_feature, float* grad_logits, float* grad_x,
                                             pasnl_stream_t stream) {
   PASNL_REQUIRE(g >= 0 && as > 0 && ch > 3, PASNL_EINVAL);
-  PASNL_REQUIRE(as <= ASG_MAX, PASNL_EUNSUPPORTED);
+  PASNL_REQUIRE(as <= AS_MAX, PASNL_EUNSUPPORTED);
   if (g == 0) return PASNL_OK;
   PASNL_REQUIRE(logits && grad_new_xyz && grad_new_feature && (grad_logits || grad_x), PASNL_ENULL);
   PASNL_REQUIRE(grad_logits == nullptr || x, PASNL_ENULL);
   // x rows = [xyz - xyz0 | xyz | feature] (3 + ch floats): coordinates and the (xyz | feature) rows both start at column 3
   const int w = 3 + ch;
-  hipLaunchKernelGGL(as_reweight_grad_kernel<true>, dim3(asg_grid((long)g * (1 + ch))), dim3(256), 0, pasnl_hip_stream(stream),
+  hipLaunchKernelGGL(as_reweight_grad_kernel<true>, dim3(as_grid((long)g * (1 + ch))), dim3(256), 0, pasnl_hip_stream(stream),
                      (long)g, as, as, ch, w, w, w, w, logits, x ? x + 3 : nullptr, x ? x + 3 : nullptr, grad_new_xyz, grad_new_feature,
                      grad_logits, grad_x, grad_x ? grad_x + 3 : nullptr);
   return pasnl_launch_status();
@@ -391,7 +343,7 @@ extern "C" int pasnl_cls_as_gather_grad(int b, int n, int c, int m, int k, int a
   float* r_xyz = reinterpret_cast<float*>(idx_as + rows);
   float* r_feat = r_xyz + (size_t)rows * 3;
   if (rows > 0) {
-    hipLaunchKernelGGL(as_gather_fold_kernel, dim3(asg_grid(rows * (3 + c))), dim3(256), 0, pasnl_hip_stream(stream), c, k, as,
+    hipLaunchKernelGGL(as_gather_fold_kernel, dim3(as_grid(rows * (3 + c))), dim3(256), 0, pasnl_hip_stream(stream), c, k, as,
                        rows * (3 + c), grad_x, idx, grad_xyz ? r_xyz : nullptr, grad_feature ? r_feat : nullptr, idx_as);
     PASNL_REQUIRE(pasnl_launch_status() == PASNL_OK, PASNL_ELAUNCH);
   }

@@ -448,7 +448,7 @@ class _ASAttention(torch.autograd.Function):
 
 
 def as_attention(q, kv):
-    """softmax(q k^T / sqrt(cb)) v per group of `as` neighbours (pointasnl_util.py:136-146), fused.
+    """softmax(q k^T / sqrt(cb)) v per group of `as` neighbours (pointasnl_util.py:136-146), fused (csrc/as_cell.hip).
     q (..., as, cb), kv (..., as, 2cb) -> (..., as, cb)
 
     Differentiable in q and kv: with gradients enabled and q or kv requiring one, the result carries a grad_fn whose backward is
@@ -532,7 +532,7 @@ class _ASReweight(torch.autograd.Function):
 
 
 def as_reweight(logits, group_xyz, group_feature, num_neighbor):
-    """AdaptiveSampling's tail (pointasnl_util.py:154,167-171) in one kernel: softmax of logits (B,P,as,1+ch) over the neighbour
+    """AdaptiveSampling's tail (pointasnl_util.py:154,167-171) in one kernel (csrc/as_cell.hip): softmax of logits (B,P,as,1+ch) over the neighbour
     axis, then the weighted sums over the first `num_neighbor` rows of group_xyz (B,P,nsample,3) and group_feature
     (B,P,nsample,ch), read in place -> new_xyz (B,P,3), new_feature (B,P,ch).  Differentiable in all three tensors (one kernel
     of csrc/as_grad.hip) when gradients are enabled and one of them requires one; otherwise the plain launch."""
@@ -621,7 +621,7 @@ class _ASGather(torch.autograd.Function):
 
 
 def as_gather(xyz, feature, idx, num_neighbor):
-    """The AdaptiveSampling cell's input rows in one launch: x (B,P,as,6+C) = [xyz[i_s] - xyz[i_0] | xyz[i_s] | feature[i_s]] for
+    """The AdaptiveSampling cell's input rows in one launch (csrc/as_cell.hip): x (B,P,as,6+C) = [xyz[i_s] - xyz[i_0] | xyz[i_s] | feature[i_s]] for
     the first as = num_neighbor columns i_s of idx (B,P,K).  Differentiable in xyz (B,N,3) and feature (B,N,C): the backward
     (csrc/as_grad.hip) sums every point's contributions in the order of the forward's output elements, without fp atomics."""
     if _needs_grad(xyz, feature):

@@ -467,7 +467,7 @@ case("fp_interpolate_cat_3x40x64x17x0", "pasnl_fp_interpolate_cat", (("n", 17, 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# cells.hip: attention
+# cells.hip: non-local attention
 # ---------------------------------------------------------------------------------------------------------------------------
 # query tiles of 32 and 64, key blocks of 32, pairs of 32-query tiles (64) in the two-tile kernel
 def _nl(b, p, n, cb, variant, ws=False, spike=False):
@@ -496,6 +496,9 @@ case("nl_attention_ws_1x100x4096", "pasnl_nl_attention_ws", (("p", 100, 64), ("p
      uses=("pasnl_nl_attention_workspace_bytes",))(_nl(1, 100, 4096, 32, 0, ws=True, spike=True))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# as_cell.hip: the AdaptiveSampling cell
+# ---------------------------------------------------------------------------------------------------------------------------
 def _as_att(g, as_, cb, form):
     def build():
         rng = rng_of("as_att", g, as_, cb, form)

@@ -1,5 +1,5 @@
-"""The fused backward of the AdaptiveSampling cell (csrc/as_grad.hip; include/pasnl.h: pasnl_cls_as_attention_grad / _qkv_grad,
-pasnl_cls_as_reweight_grad / _x_grad, pasnl_cls_as_gather_grad) through pointasnl_util's autograd functions, through the C ABI
+"""The fused backward of the AdaptiveSampling cell (csrc/as_grad.hip, on csrc/as_core.hpp with the forward in csrc/as_cell.hip;
+include/pasnl.h: pasnl_cls_as_attention_grad / _qkv_grad, pasnl_cls_as_reweight_grad / _x_grad, pasnl_cls_as_gather_grad) through pointasnl_util's autograd functions, through the C ABI
 and through adaptive_sampling_fused.
 
 Reference: tests/as_grad_ref.py, the header's formulas in float64.  Measure: err(X) = max |X - X64| / max |X64| per gradient.
