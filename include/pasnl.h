@@ -641,6 +641,56 @@ int pasnl_cls_sa_group_grad(int b, int n, int c, int m, int k, const float* xyz,
                             float* grad_feature, float* grad_new_xyz, void* workspace, size_t workspace_bytes,
                             pasnl_stream_t stream);
 
+/* Training-mode batch norm (csrc/bn_train.hip; reference utils/tf_util.py:512-531, batch_norm_template with is_training=True:
+ * tf.contrib.layers.batch_norm(decay=bn_decay, updates_collections=None, epsilon 1e-3)).  x is a (rows, c) float32 matrix, row-
+ * major, the channel last -- a GEMM's output; every statistic is over rows.  (pasnl_cls_ prefix: see above.)
+ *
+ * pasnl_cls_bn_train: per column j, in float64 from float64 sums of x and x^2,
+ *     mean_j = sum_r x[r,j] / rows     var_j = max(sum_r x[r,j]^2 / rows - mean_j^2, 0)  (biased)     rstd_j = 1 / sqrt(var_j + eps)
+ * rounded to float32 into save_mean (c) and save_rstd (c), and in float32, each operation rounded on its own,
+ *     y[r,j] = act(((x[r,j] - mean_j) * rstd_j) * gamma_j + beta_j)                 act: 0 none, 1 ReLU
+ * moving_mean / moving_var (c): both NULL = no update; else updated in place as assign_moving_average(zero_debias=False) does,
+ *     m <- m - (m - batch) * (1 - decay)       batch = mean_j, and for the variance var_j * rows / max(rows - 1, 1) when
+ * unbiased != 0 (TF's fused kernel, with its rows == 1 guard), else var_j.  y must not overlap x.
+ *
+ * pasnl_cls_bn_train_grad: with g = grad_y [y > 0] when act == 1, else grad_y (y is then not read and may be NULL), and
+ * xhat = (x - save_mean) * save_rstd in float32:
+ *     grad_beta_j = sum_r g[r,j]      grad_gamma_j = sum_r g[r,j] xhat[r,j]             (float64 sums, rounded to float32)
+ *     grad_x[r,j] = (gamma_j * rstd_j) * ((g[r,j] - grad_beta_j / rows) - xhat[r,j] * (grad_gamma_j / rows))
+ * grad_x == NULL skips that pass; grad_gamma and grad_beta are always written.  grad_x must not overlap an input.
+ *
+ * Deterministic: no atomics; a thread adds its rows in ascending order, a workgroup folds its threads by a fixed tree and writes
+ * one float64 partial per column and slab into the workspace, a second launch adds the slabs in a fixed order: the results are
+ * a pure function of the arguments.  16-byte accesses where c % 4 == 0 and x, y, grad_y, grad_x are 16-byte aligned, else 4-byte
+ * ones.  rows <= 128 is ONE launch.
+ * workspace (both entries): pasnl_cls_bn_train[_grad]_workspace_bytes(rows, c) =
+ *     16 c min(ceil(rows / 256), max(1, 2048 / ceil(c / 256)))        (0 for rows <= 0 or c <= 0; integer division)
+ * bytes, 8-byte aligned; its contents before the call do not matter.
+ * Checked in this order, before anything is enqueued: rows >= 0, c > 0, act in {0, 1}, and for the forward eps > 0 and
+ * 0 <= decay <= 1, else PASNL_EINVAL; rows == 0 is a successful no-op; a NULL matrix, vector or output (the forward: x, gamma,
+ * beta, y, save_mean, save_rstd, or exactly one of the moving pair; the backward: x, y with act == 1, gamma, save_mean,
+ * save_rstd, grad_y, grad_gamma, grad_beta) PASNL_ENULL; a matrix pointer that is not 4-byte aligned, a workspace that is not
+ * 8-byte aligned, or rows > 2^40, PASNL_EUNSUPPORTED; a NULL or short workspace PASNL_EWORKSPACE. */
+size_t pasnl_cls_bn_train_workspace_bytes(long rows, int c);
+int pasnl_cls_bn_train(long rows, int c, const float* x, const float* gamma, const float* beta, float eps, float decay, int act,
+                       int unbiased, float* moving_mean, float* moving_var, float* y, float* save_mean, float* save_rstd,
+                       void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+size_t pasnl_cls_bn_train_grad_workspace_bytes(long rows, int c);
+int pasnl_cls_bn_train_grad(long rows, int c, const float* x, const float* y, const float* gamma, const float* save_mean,
+                            const float* save_rstd, int act, const float* grad_y, float* grad_x, float* grad_gamma,
+                            float* grad_beta, void* workspace, size_t workspace_bytes, pasnl_stream_t stream);
+
+/* pasnl_cls_dropout (csrc/bn_train.hip; reference utils/tf_util.py:594-615, tf.nn.dropout(inputs, keep_prob) in training):
+ *     y[i] = x[i] / keep_prob  where element i is kept, else 0            (float32 division; y may be x)
+ * Element i is kept iff (w >> 8) * 2^-24 < keep_prob (float32, exact), w = word (i & 3) of the Philox4x32-10 block at
+ *     key (seed lo, seed hi),  counter ((i >> 2) lo, (i >> 2) hi, call, stream_id)
+ * -- the generator of pasnl_scan_augment.  No mask is stored: the backward is the same call on the incoming gradient with the
+ * same (seed, stream_id, call).  TensorFlow's own generator is not reproduced.
+ * Checked in this order, before anything is enqueued: n >= 0 and 0 < keep_prob <= 1, else PASNL_EINVAL; n == 0 is a successful
+ * no-op; NULL x or y PASNL_ENULL; a pointer that is not 4-byte aligned, or n > 2^40, PASNL_EUNSUPPORTED. */
+int pasnl_cls_dropout(long n, float keep_prob, unsigned long long seed, unsigned stream_id, unsigned call, const float* x, float* y,
+                      pasnl_stream_t stream);
+
 /* Tail of a set-abstraction layer, fused (pointasnl_util.py:258-261 skip connection, :213-216 back-projection of the
  * non-local cell, :282-290 the two adds and the aggregation layer):
  *   out = relu( ( after + relu(skip_max ws + bs) + relu(att wb + bb) ) wagg + bagg )

@@ -31,6 +31,7 @@ SYMBOLS = [
     "pasnl_cls_tail_group_all", "pasnl_cls_tail_mlp2", "pasnl_cls_nl_cell_input", "pasnl_cls_nl_cell_input_grad_workspace_bytes", "pasnl_cls_nl_cell_input_grad", "pasnl_cls_nl_attention_grad_workspace_bytes", "pasnl_cls_nl_attention_grad",
     "pasnl_cls_as_attention_grad", "pasnl_cls_as_attention_qkv_grad", "pasnl_cls_as_reweight_grad", "pasnl_cls_as_reweight_x_grad", "pasnl_cls_as_gather_grad_workspace_bytes", "pasnl_cls_as_gather_grad",
     "pasnl_cls_sa_local_cell_grad_workspace_bytes", "pasnl_cls_sa_local_cell_grad", "pasnl_cls_sa_group_grad_workspace_bytes", "pasnl_cls_sa_group_grad",
+    "pasnl_cls_bn_train_workspace_bytes", "pasnl_cls_bn_train", "pasnl_cls_bn_train_grad_workspace_bytes", "pasnl_cls_bn_train_grad", "pasnl_cls_dropout",
     "pasnl_block_key_capacity", "pasnl_block_crop_stats", "pasnl_block_grid_count", "pasnl_block_fill", "pasnl_block_gather", "pasnl_block_normalize", "pasnl_block_score_workspace_bytes", "pasnl_block_score", "pasnl_block_train_batch", "pasnl_block_train_score",
     "pasnl_kblock_crop_stats", "pasnl_kblock_grid_count", "pasnl_kblock_fill", "pasnl_kblock_gather", "pasnl_kblock_rotate",
     "pasnl_grad_workspace_bytes", "pasnl_gather_point_grad_det", "pasnl_group_point_grad_det", "pasnl_three_interpolate_grad_det",
@@ -82,6 +83,16 @@ def lib():
         _lib.pasnl_window_hist_bytes.restype = ctypes.c_size_t
         _lib.pasnl_kwindow_hist_bytes.restype = ctypes.c_size_t
         _lib.pasnl_block_score_workspace_bytes.restype = ctypes.c_size_t
+        # csrc/bn_train.hip takes long, float and 64-bit arguments by value: their types are stated, nothing is left to
+        # ctypes' defaults (int for a Python int, no float at all)
+        P, L, I, F, Z = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+        for name in ("pasnl_cls_bn_train_workspace_bytes", "pasnl_cls_bn_train_grad_workspace_bytes"):
+            getattr(_lib, name).argtypes, getattr(_lib, name).restype = [L, I], Z
+        _lib.pasnl_cls_bn_train.argtypes = [L, I, P, P, P, F, F, I, I, P, P, P, P, P, P, Z, P]
+        _lib.pasnl_cls_bn_train_grad.argtypes = [L, I, P, P, P, P, P, I, P, P, P, P, P, Z, P]
+        _lib.pasnl_cls_dropout.argtypes = [L, F, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P, P, P]
+        for name in ("pasnl_cls_bn_train", "pasnl_cls_bn_train_grad", "pasnl_cls_dropout"):
+            getattr(_lib, name).restype = I
         for s in SYMBOLS:
             getattr(_lib, s)  # AttributeError here == header / library mismatch
     return _lib

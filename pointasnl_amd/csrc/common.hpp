@@ -239,6 +239,22 @@ __device__ __forceinline__ void knn_flag_query(const KnnTieFlags f, int bi, int 
   if (lane == 0) f.flist[(size_t)bi * m + atomicAdd(&f.nflag[bi], 1)] = j;
 }
 
+// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+struct Philox4 {
+  unsigned w[4];
+};
+__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+__device__ __forceinline__ float philox_uniform(unsigned w) { return (float)(w >> 8) * 0x1p-24f; }  // [0,1), exact
+
 // The library reads no environment variable and keeps no global state (include/pasnl.h), so a launch is a pure function
 // of its arguments.
 

@@ -58,21 +58,8 @@ __global__ __launch_bounds__(GT_THREADS) void train_labels_kernel(int num_point,
   out_weights[e] = (weights && l >= 0 && l < nw) ? weights[l] : 0.0f;
 }
 
-// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-struct Philox4 {
-  unsigned w[4];
-};
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return Philox4{{c0, c1, c2, c3}};
-}
-__device__ __forceinline__ float gt_uniform(unsigned w) { return (float)(w >> 8) * 0x1p-24f; }  // [0,1), exact
+// (Philox4x32-10 and its float32 uniform live in common.hpp: the dropout of bn_train.hip draws from the same generator)
+__device__ __forceinline__ float gt_uniform(unsigned w) { return philox_uniform(w); }
 
 // Box-Muller: radius from u1 = ((wa >> 8) + 1) * 2^-24 in (0,1], angle 2 pi u2 with u2 = (wb >> 8) * 2^-24 (the sine and the
 // cosine take 2 u2 in half turns: no rounded angle) -> (r cos, r sin)

@@ -40,6 +40,8 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     # the two pooled vectors are written side by side into fc1's input: tf.concat([l3_points, l3_points_res]) for free
     # (allocated up here: layer 1's last kernel runs layer3_1 on its own rows where it can -- `group_all` below)
     net = torch.empty((batch_size, 1024 + 512), dtype=torch.float32, device=point_cloud.device)
+    # (training mode: the pooled vectors are tensors of the graph and are concatenated below, as the reference does)
+    training = tf_util._training(is_training)
     # with adaptive sampling the fused launch measured 0.5 % SLOWER per step (EXPERIMENTS.md, "Layer 1's tail inside layer3_1's
     # kernel"; supposed, not traced: layer 2's search is forked inside the forward there and now waits behind layer3_1's tiles):
     # two launches unless asked for
@@ -78,11 +80,14 @@ def get_model(point_cloud, is_training=False, use_normal=False, bn_decay=None, w
     if getattr(l1_points, "group_all_pooled", None) is None:  # (else layer 1's last kernel ran layer3_1 as well: net[:, 1024:] is written)
         _, l3_points_res, _ = pointnet_sa_module(l1_xyz, l1_points, npoint=None, radius=None, nsample=None,
                                                  mlp=[128, 256, 512], mlp2=None, group_all=True, is_training=is_training,
-                                                 bn_decay=bn_decay, scope='layer3_1', pooled_out=net[:, 1024:])
+                                                 bn_decay=bn_decay, scope='layer3_1', pooled_out=None if training else net[:, 1024:])
     if getattr(l2_points, "group_all_pooled", None) is None:  # (else layer 2's tail ran layer3_2 as well: net[:, :1024] is written)
         _, l3_points, _ = pointnet_sa_module(l2_xyz, l2_points, npoint=None, radius=None, nsample=None,
                                              mlp=[256, 512, 1024], mlp2=None, group_all=True, is_training=is_training,
-                                             bn_decay=bn_decay, scope='layer3_2', pooled_out=net[:, :1024])
+                                             bn_decay=bn_decay, scope='layer3_2', pooled_out=None if training else net[:, :1024])
+
+    if training:
+        net = torch.cat([l3_points.reshape(batch_size, -1), l3_points_res.reshape(batch_size, -1)], dim=-1)
 
     # Fully connected layers
     net = tf_util.fully_connected(net, 512, bn=True, is_training=is_training, scope='fc1', bn_decay=bn_decay)

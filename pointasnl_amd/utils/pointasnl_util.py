@@ -241,13 +241,13 @@ def _layer_uncached(st, cin, cout, bn, weight_decay):
     names = [key + leaf for leaf in ("weights", "biases", "bn/gamma", "bn/beta")]
     if not (torch.is_grad_enabled() and any(st.vars[n].requires_grad for n in names if n in st.vars)):
         return st.layer(cin, cout, bn, weight_decay)
-    cached = st._folded.pop(key, None)
+    cached = st._folded.take(key)
     try:
         return st.layer(cin, cout, bn, weight_decay)
     finally:
         st._folded.pop(key, None)
-        if cached is not None and not any(t.requires_grad for t in cached):
-            st._folded[key] = cached
+        if cached is not None and not any(t.requires_grad for t in cached[0]):
+            st._folded.put_back(key, cached)
 
 
 def sa_local_cell(new_point, mlp, is_training, bn_decay, weight_decay, bn):
@@ -255,6 +255,7 @@ def sa_local_cell(new_point, mlp, is_training, bn_decay, weight_decay, bn):
     centred coordinates, and H2^T . G, in one MFMA kernel.  (B,P,K,6+C) -> (B,P,mlp[1],32) = the input of after_conv.
     The variables are the same ones the op-by-op chain would create (scopes conv0, conv1, weight_net/wconv0).  The batch-norm
     fold is torch's, so with sa_local_cell_w's backward the gradients reach weights, biases, gamma and beta."""
+    tf_util._require_inference(is_training)
     b, p, k, w = new_point.shape
     c1, c2 = mlp[0], mlp[1]
     st = tf_util.store()
@@ -325,6 +326,7 @@ def sa_cell(xyz, feature, idx, new_xyz, mlp, is_training, bn_decay, weight_decay
     kernel, which also takes the skip connection's max over the K neighbours.
     -> (B,P,c,32) = the input of after_conv (c = the width of the last convolution; a view of the kernel's 32-channel
        output when c = 16),  skip (B,P,6+C)"""
+    tf_util._require_inference(is_training)
     b, n, c = feature.shape
     _, p, k = idx.shape
     native16 = SA_CELL16 and len(mlp) == 3 and mlp[0] == 16 and c == 3 and k == 32 and new_xyz is not None
@@ -391,6 +393,7 @@ def sa_cell_pre(xyz, feature, idx, new_xyz, mlp, is_training, bn_decay, weight_d
     """sa_cell with conv0 split at its linear part: [xyz | feature] . W0[3:] + b0 once per source point (pasnl_sa_project), then
     the cell adds (xyz - centre) . W0[0:3] to the gathered rows of that table (pasnl_sa_cell_pre / _centre0).  Same variables,
     same outputs as sa_cell; `out` within fp32 rounding of it, `skip` bit-equal.  new_xyz = None: the centres are neighbour 0."""
+    tf_util._require_inference(is_training)
     b, n, c = feature.shape
     _, p, k = idx.shape
     xyz, feature, idx = xyz.contiguous(), feature.contiguous(), idx.contiguous()
@@ -923,10 +926,11 @@ def PointNonLocalCell(feature, new_point, mlp, is_training, bn_decay, weight_dec
     with tf_util.variable_scope(scope):
         bottleneck_channel = mlp[0]
         batch_size, npoint, nsample, channel = new_point.shape
-        if NL_NARROW_PROJECT and feature.shape[-1] <= 16 and channel <= 16 and bottleneck_channel in (32, 64, 128):
+        if (NL_NARROW_PROJECT and feature.shape[-1] <= 16 and channel <= 16 and bottleneck_channel in (32, 64, 128)
+                and not tf_util._training(is_training)):
             # coordinates in, keys|values and queries out: both projections as ONE streaming kernel (two GEMMs with K = 3 / 6
-            # are bound by their own start-up); the variables are the ones conv2d creates (scopes conv_kv, conv_query)
-            tf_util._require_inference(is_training)
+            # are bound by their own start-up); the variables are the ones conv2d creates (scopes conv_kv, conv_query).
+            # (The kernels take BN-folded weights: training goes through conv2d's batch statistics below, then nl_attention.)
             st = tf_util.store()
             with tf_util.variable_scope('conv_kv'):
                 wkv, bkv = st.layer(feature.shape[-1], 2 * bottleneck_channel, bn, weight_decay)
@@ -1243,8 +1247,12 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         # A gradient is asked for (gradients enabled and xyz, feature or a variable of the layer requires one): the differentiable
         # route -- sa_group, sa_local_cell (or the torch chain), the op-by-op tail -- instead of the raw launches below, whose
         # results carry no grad_fn.  With nothing requiring a gradient the dispatch and its bits are unchanged.
+        # Training mode (is_training=True) takes none of the fused cells, tails or samplers below -- they fold batch norm with its
+        # MOVING statistics -- but the op-by-op chain, where every convolution is a tf_util wrapper (the only place batch
+        # statistics are taken) and the data movement is the differentiable ops' (sa_group, group_point, nl_attention, ...).
+        train = tf_util._training(is_training)
         st_path = tf_util.store().path("")
-        diff = not is_training and torch.is_grad_enabled() and (
+        diff = not train and torch.is_grad_enabled() and (
             xyz.requires_grad or feature.requires_grad
             or any(v.requires_grad for name, v in tf_util.store().vars.items() if name.startswith(st_path)))
 
@@ -1264,16 +1272,15 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
             # the fused cell finds its centres in its own tiles and writes new_xyz / new_feature itself: no gather launch
             # between the search and the cell (pasnl_sa_cell_centre0)
             # (rows wider than 128 channels: only the wide kernels -- mlp[0] = 256 / 512 -- write the neighbour-0 row themselves)
-            centre0 = (not diff and CENTRE0 and fused and SA_CELL_GATHER and npoint <= num_points
+            centre0 = (not diff and not train and CENTRE0 and fused and SA_CELL_GATHER and npoint <= num_points
                        and (num_channel <= 128 or (SA_CELL_WIDE and mlp[0] in (256, 512) and nsample == 32)))
-            if diff:
+            if diff or (train and torch.is_grad_enabled()):
                 idx0 = idx[:, :, 0].contiguous()  # (group_point has a backward; pasnl_take_neighbor0 is a raw launch)
                 new_xyz = _gather_rows(xyz, idx0)
                 new_feature = torch.cat([new_xyz, _gather_rows(feature, idx0)], dim=-1)
             elif not centre0:
                 new_xyz, new_feature = take0()
-        elif num_points != npoint and AS_FUSED and as_neighbor <= 16:
-            tf_util._require_inference(is_training)
+        elif num_points != npoint and AS_FUSED and as_neighbor <= 16 and not train:
             new_xyz, new_feature = adaptive_sampling_fused(xyz, feature, idx, as_neighbor, scope, bn, weight_decay)
         elif num_points != npoint:
             # AdaptiveSampling only ever reads the first `as_neighbor` neighbours (:165-166): gather just those
@@ -1287,9 +1294,8 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         if after_sampling is not None and not centre0:
             after_sampling(new_xyz)  # the sampled (and shifted) coordinates are final: the caller may start the next search
         new_point = None
-        if fused and SA_CELL_GATHER and not diff:
+        if fused and SA_CELL_GATHER and not diff and not train:
             # grouping + skip max + local cell: one MFMA kernel reading the tables in place
-            tf_util._require_inference(is_training)
             # (the table pays where every source point is gathered many times; both centre forms take the same route)
             cell = sa_cell_pre if sa_cell_pre_supported(batch_size, num_points, num_channel, npoint, nsample, mlp, feature) else sa_cell
             try:
@@ -1311,8 +1317,9 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
             grouped_xyz = new_point[..., 0:3]
             if fused and not (len(mlp) == 3 and mlp[0] >= 32):
                 fused = False  # the two-kernel form exists for the plain [c, c, out] shape only
+            if train:
+                fused = False  # sa_local_cell folds batch norm: the chain below takes the batch's statistics
             if fused:
-                tf_util._require_inference(is_training)
                 try:
                     new_point = sa_local_cell(new_point, mlp, is_training, bn_decay, weight_decay, bn)
                 except _hip.PasnlUnsupported:
@@ -1333,10 +1340,9 @@ def PointASNLSetAbstraction(xyz, feature, npoint, nsample, mlp, is_training, bn_
         c_out = mlp[-1]
         # (layers with few groups -- the deep, wide ones: 512 rows x 512 channels -- are 16 workgroups of dependent MFMA
         # chains fed from L2; there the three small vendor GEMMs are faster: measured 101 vs ~45 us)
-        if SA_TAIL_FUSED and not diff and c_out % 32 == 0 and c_out <= 512 and batch_size * npoint >= SA_TAIL_MIN_ROWS:
+        if SA_TAIL_FUSED and not diff and not train and c_out % 32 == 0 and c_out <= 512 and batch_size * npoint >= SA_TAIL_MIN_ROWS:
             # skip convolution + back-projection of the non-local cell + both adds + aggregation: ONE kernel behind the
             # after_conv GEMM (pasnl_sa_tail) instead of three small GEMMs and two element-wise passes
-            tf_util._require_inference(is_training)
             cb = max(32, num_channel // 2)
             att = None
             if NL:
@@ -1512,16 +1518,16 @@ def PointASNLDecodingLayer(xyz1, xyz2, points1, points2, nsample, mlp, is_traini
         # nn = three_nn(xyz1, xyz2), knn_all = the self-kNN of xyz1 (B,N1,K>=nsample): both read coordinates only and may
         # have been computed ahead by the caller (tuple / tensor / Forked); the encoder layer of this level shares knn_all
         dist, idx = three_nn(xyz1, xyz2) if nn is None else _resolved(nn)
-        if FP_HEAD_FUSED and not is_training and not torch.is_grad_enabled():
+        if FP_HEAD_FUSED and not tf_util._training(is_training) and not torch.is_grad_enabled():
             interpolated_points = fp_interpolate_cat(points2, idx, dist)  # weights + interpolation in one launch, the same bits
         else:
             weight = three_weights(dist)  # pointasnl_util.py:308-311 as one kernel
             interpolated_points = three_interpolate(points2, idx, weight)
 
         # ---- local cell (:322-331)
-        if DECODE_CELL_FUSED and use_xyz and use_knn and nsample in (16, 32):
-            # self-kNN, both gathers, the centring, the weight net and F^T.G in one kernel (no grouped tensors)
-            tf_util._require_inference(is_training)
+        if DECODE_CELL_FUSED and use_xyz and use_knn and nsample in (16, 32) and not tf_util._training(is_training):
+            # self-kNN, both gathers, the centring, the weight net and F^T.G in one kernel (no grouped tensors; the weight net's
+            # batch norm folded, so inference only: training takes the chain below)
             if knn_all is None:
                 kidx = knn_query(nsample, xyz1, xyz1)
             else:  # ascending (distance, index): the first nsample columns of a wider self-kNN ARE the nsample-NN

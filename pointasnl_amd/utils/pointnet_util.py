@@ -181,7 +181,11 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
         else:
             new_xyz, new_points, idx, grouped_xyz = sample_and_group(npoint, radius, nsample, xyz, points, knn, use_xyz)
         fused = None
-        if group_all and len(mlp) == 3 and mlp[0] in GROUP_ALL_FUSED and new_points.is_cuda and not is_training:
+        train = tf_util._training(is_training)
+        if train and pooled_out is not None:
+            raise ValueError("pointnet_sa_module: pooled_out is a buffer the inference kernels write into; training mode returns its "
+                             "pooled rows as a tensor of the graph")
+        if group_all and len(mlp) == 3 and mlp[0] in GROUP_ALL_FUSED and new_points.is_cuda and not train:
             try:
                 fused = group_all_mlp_max(new_points, mlp, bn, pooled_out.reshape(-1, mlp[-1]) if pooled_out is not None else None)
             except _hip.PasnlUnsupported:
@@ -193,7 +197,11 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
                 new_points = tf_util.conv2d(new_points, num_out_channel, [1, 1], padding='VALID', stride=[1, 1], bn=bn,
                                             is_training=is_training, scope='conv%d' % (i), bn_decay=bn_decay,
                                             input_pad=getattr(new_points, "input_pad", 0) if i == 0 else 0)
-            new_points = max_pool_points(new_points, out=pooled_out)
+            if train and torch.is_grad_enabled() and new_points.requires_grad:
+                # tf.reduce_max with its gradient (shared evenly among ties): pasnl_max_pool_rows is a raw launch without one
+                new_points = torch.amax(new_points, dim=2, keepdim=True)
+            else:
+                new_points = max_pool_points(new_points, out=pooled_out)
         if mlp2 is not None:
             for i, num_out_channel in enumerate(mlp2):
                 new_points = tf_util.conv2d(new_points, num_out_channel, [1, 1], padding='VALID', stride=[1, 1], bn=bn,
@@ -213,7 +221,7 @@ def pointnet_fp_module(xyz1, xyz2, points1, points2, mlp, is_training, bn_decay,
     '''
     with tf_util.variable_scope(scope):
         dist, idx = three_nn(xyz1, xyz2) if nn is None else (nn.get() if hasattr(nn, "get") else nn)
-        if FP_HEAD_FUSED and not is_training and not torch.is_grad_enabled():
+        if FP_HEAD_FUSED and not tf_util._training(is_training) and not torch.is_grad_enabled():
             # weights + interpolation + concat in one launch, the same bits (pasnl_fp_interpolate_cat)
             new_points1 = fp_interpolate_cat(points2, idx, dist, points1)
         else:

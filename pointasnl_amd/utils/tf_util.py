@@ -1,5 +1,6 @@
-"""tf_util -- host-side mirror of the reference's layer wrappers (utils/tf_util.py:52,120,327,512,594),
-inference only, on torch.
+"""tf_util -- host-side mirror of the reference's layer wrappers (utils/tf_util.py:52,120,327,512,594) on torch: the
+inference graph (batch norm folded into the GEMM) and, with is_training=True, the training graph (batch statistics, moving
+averages, dropout: csrc/bn_train.hip).
 
 The reference builds TF variables under ``tf.variable_scope``; here a ``VariableStore`` plays that role: a
 layer looks its variables up by scope path (``layer1/conv_kv/weights`` ...) and creates them on first use from
@@ -25,6 +26,72 @@ FUSE_RELU_EPILOGUE = True
 WEIGHTS_TRANSPOSED_MIN_K = 2048  # dense layers contracting at least this many inputs keep their weights transposed (see _dense)
 
 
+class _FoldCache(dict):
+    """VariableStore._folded: BN-folded weights and what is derived from them (padded, transposed, reordered, concatenated,
+    packed), each entry with the variables it was built from and their `_version` at that time.
+
+    Training changes those variables in place behind the cache (the moving update of batch_norm_train, an optimizer's step()),
+    so an entry is only served while every one of its sources still has the version it was built from.  The writers keep their
+    idiom -- `if key not in cache: cache[key] = build()`, then `cache[key]` -- and the sources are recorded for them: a miss
+    opens a recording, VariableStore.get() and every read of another entry add what they touch to the open recordings, and the
+    assignment closes its key's.  An entry derived from a folded tensor alone (keyed by that tensor's pointer) records nothing;
+    it is found only through a tensor that was validated in the same call, and the first stale entry met drops the WHOLE cache,
+    as `assign` does, so it cannot outlive its parent."""
+
+    def __init__(self):
+        super().__init__()
+        self._sources = {}  # key -> ((tensor, _version), ...)
+        self._open = []     # [key, [tensor, ...]] of the misses whose entry is being built
+
+    def touch(self, tensors):
+        tensors = list(tensors)
+        for frame in self._open:
+            frame[1].extend(tensors)
+
+    def __contains__(self, key):
+        if dict.__contains__(self, key):
+            if all(t._version == v for t, v in self._sources.get(key, ())):
+                return True
+            self.clear()
+        self._open = [f for f in self._open if f[0] != key]  # (a recording whose builder raised)
+        self._open.append([key, []])
+        return False
+
+    def __getitem__(self, key):
+        value = dict.__getitem__(self, key)
+        if self._open:
+            self.touch(t for t, _ in self._sources.get(key, ()))
+        return value
+
+    def __setitem__(self, key, value):
+        seen = []
+        for i in range(len(self._open) - 1, -1, -1):
+            if self._open[i][0] == key:
+                seen = self._open[i][1]
+                del self._open[i:]
+                break
+        self._sources[key] = tuple({id(t): (t, t._version) for t in seen}.values())
+        dict.__setitem__(self, key, value)
+
+    def take(self, key):
+        """remove `key` -> (value, sources) for put_back, or None"""
+        if not dict.__contains__(self, key):
+            return None
+        return dict.pop(self, key), self._sources.pop(key, ())
+
+    def put_back(self, key, taken):
+        dict.__setitem__(self, key, taken[0])
+        self._sources[key] = taken[1]
+
+    def pop(self, key, default=None):
+        self._sources.pop(key, None)
+        return dict.pop(self, key, default)
+
+    def clear(self):
+        dict.clear(self)
+        self._sources.clear()
+
+
 class VariableStore:
     """Seeded variable container + scope stack (the stand-in for TF's graph collections)."""
 
@@ -34,8 +101,9 @@ class VariableStore:
         self.randomize_bn = randomize_bn  # non-trivial gamma/beta/mean/var so that BN folding is actually tested
         self.vars = {}
         self.decays = {}  # weights variable -> wd: the reference's 'losses' collection (tf_util.py:30-49: wd * l2_loss(var))
-        self._folded = {}
+        self._folded = _FoldCache()
         self._scope = []
+        self.dropout_calls = 0  # the `call` word of the next training-mode dropout's mask (settable: a test replays a mask)
 
     # ---- scopes
     @contextlib.contextmanager
@@ -118,23 +186,43 @@ class VariableStore:
             else:
                 raise ValueError(kind)
             self.vars[full] = torch.tensor(v, dtype=torch.float32, device=self.device)
+        if self._folded._open:
+            self._folded.touch((self.vars[full],))
         return self.vars[full]
 
+    def variables(self, cin, cout, bn):
+        """(weights, biases, gamma, beta, moving_mean, moving_variance) of the layer at the current scope, as stored (the last
+        four None without bn), created on first use"""
+        w = self.get("weights", (cin, cout), "xavier")
+        b = self.get("biases", (cout,), "small" if self.randomize_bn else "zeros")
+        if not bn:
+            return w, b, None, None, None, None
+        with self.scope("bn"):
+            gamma = self.get("gamma", (cout,), "positive" if self.randomize_bn else "ones")
+            beta = self.get("beta", (cout,), "small" if self.randomize_bn else "zeros")
+            mean = self.get("moving_mean", (cout,), "small" if self.randomize_bn else "zeros")
+            var = self.get("moving_variance", (cout,), "positive" if self.randomize_bn else "ones")
+        return w, b, gamma, beta, mean, var
+
+    def trainable(self, requires_grad=True):
+        """{name: tensor} of every weights, biases, gamma and beta the store holds (never a moving statistic: those are updated by
+        the training-mode batch norm itself), with requires_grad set on them: `torch.optim.SGD(store.trainable().values(), ...)`.
+        Variables are created by the first call of their layer: run the model once (or load a checkpoint) first."""
+        out = {}
+        for name, t in self.vars.items():
+            if name.split("/")[-1] in ("weights", "biases", "gamma", "beta"):
+                out[name] = t.requires_grad_(bool(requires_grad))
+        return out
+
     def layer(self, cin, cout, bn, weight_decay=None):
-        """(W', b') of the layer at the current scope, BN folded, cached.  weight_decay: as the reference's
+        """(W', b') of the layer at the current scope, BN folded, cached until one of its variables changes.  weight_decay: as the reference's
         _variable_with_weight_decay, a layer built with one contributes wd * l2_loss(weights) to get_loss()."""
         if weight_decay is not None:
             self.decays[self.path("weights")] = float(weight_decay)
         key = self.path("")
         if key not in self._folded:
-            w = self.get("weights", (cin, cout), "xavier")
-            b = self.get("biases", (cout,), "small" if self.randomize_bn else "zeros")
+            w, b, gamma, beta, mean, var = self.variables(cin, cout, bn)
             if bn:
-                with self.scope("bn"):
-                    gamma = self.get("gamma", (cout,), "positive" if self.randomize_bn else "ones")
-                    beta = self.get("beta", (cout,), "small" if self.randomize_bn else "zeros")
-                    mean = self.get("moving_mean", (cout,), "small" if self.randomize_bn else "zeros")
-                    var = self.get("moving_variance", (cout,), "positive" if self.randomize_bn else "ones")
                 s = gamma / torch.sqrt(var + BN_EPS)
                 w, b = w * s, (b - mean) * s + beta
             self._folded[key] = (w.contiguous(), b.contiguous())
@@ -176,8 +264,198 @@ def variable_scope(name):
 
 
 def _require_inference(is_training):
-    if is_training not in (False, None):
-        raise NotImplementedError("pointasnl_amd mirrors the inference graph only (is_training must be False)")
+    """for the fused inference kernels, which take BN-folded weights: they have no training form"""
+    if _training(is_training):
+        raise NotImplementedError("this fused kernel folds batch norm with its moving statistics (is_training must be False)")
+
+
+def _training(is_training):
+    """is_training as a Python bool.  The reference feeds a placeholder; here the mode picks the code path on the host, so a
+    tensor is refused instead of being read back from the device."""
+    if isinstance(is_training, torch.Tensor):
+        raise TypeError("is_training must be a Python bool (or None), not a tensor: the mode is chosen on the host")
+    if is_training is None or isinstance(is_training, (bool, np.bool_)):
+        return bool(is_training)
+    if is_training in (0, 1):
+        return bool(is_training)
+    raise TypeError(f"is_training must be a Python bool (or None), got {type(is_training).__name__}")
+
+
+# ---- training mode (reference utils/tf_util.py:512-531 batch norm with batch statistics, :594-615 dropout)
+BN_TRAIN_FUSED = True  # False: the same training semantics on torch ops (the A/B partner and the tests' yardstick)
+BN_TRAIN_TORCH_DTYPE = None  # the torch route's statistics type (batch_norm_train_torch's dtype): torch.float64 = the tests' yardstick
+_BN_TRAIN_WS = {}
+
+
+def _bn_unbiased(rank):
+    """Whether the moving VARIANCE is fed Bessel's correction, by the rank of the layer's input -- stated from the TF 1.x
+    sources as remembered (TensorFlow is not available to this project): tf.contrib.layers.batch_norm sends rank 2 and rank 4
+    inputs (fully_connected, conv2d) to _fused_batch_norm, whose kernel returns var * n / max(n - 1, 1) for the moving
+    average; rank 3 (conv1d) takes the tf.nn.moments path, which is uncorrected."""
+    return rank in (2, 4)
+
+
+def _bn_decay_value(bn_decay):
+    """float, None (tf.contrib's default is overridden by the reference's `bn_decay if bn_decay is not None else 0.9`), a 0-dim
+    tensor or a callable (the trainers' schedule), read at the call"""
+    if bn_decay is None:
+        return 0.9
+    if callable(bn_decay) and not isinstance(bn_decay, torch.Tensor):
+        bn_decay = bn_decay()
+    return float(bn_decay)
+
+
+def _bn_train_workspace(nbytes, device):
+    """scratch of pasnl_cls_bn_train / _grad, cached as _dense_rows_workspace caches its own: one list per (device, stream),
+    buffers only ever added"""
+    key = (device.index, torch.cuda.current_stream().cuda_stream)
+    bufs = _BN_TRAIN_WS.setdefault(key, [])
+    if not bufs or bufs[-1].numel() < nbytes:
+        bufs.append(torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device))
+    return bufs[-1]
+
+
+class _BatchNormTrain(torch.autograd.Function):
+    """pasnl_cls_bn_train and pasnl_cls_bn_train_grad over a contiguous (rows, c) float32 matrix"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, decay, act, unbiased):
+        rows, c = x.shape
+        y = torch.empty_like(x)
+        save_mean, save_rstd = x.new_empty((c,)), x.new_empty((c,))
+        nbytes = int(_hip.lib().pasnl_cls_bn_train_workspace_bytes(rows, c))
+        ws = _bn_train_workspace(nbytes, x.device)
+        _hip.launch("pasnl_cls_bn_train", "bn_train", rows, c, _hip.ptr(x), _hip.ptr(gamma), _hip.ptr(beta), BN_EPS, decay, act,
+                    int(unbiased), _hip.ptr(moving_mean), _hip.ptr(moving_var), _hip.ptr(y), _hip.ptr(save_mean), _hip.ptr(save_rstd),
+                    _hip.ptr(ws), nbytes)
+        for t in (moving_mean, moving_var):
+            if t is not None:  # written behind torch's back: the folded caches watch `_version`
+                torch.autograd.graph.increment_version(t)
+        ctx.save_for_backward(x, y if act else None, gamma, save_mean, save_rstd)
+        ctx.act = act
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        x, y, gamma, save_mean, save_rstd = ctx.saved_tensors
+        rows, c = x.shape
+        grad_y = grad_y.contiguous()
+        grad_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        grad_gamma, grad_beta = x.new_empty((c,)), x.new_empty((c,))
+        nbytes = int(_hip.lib().pasnl_cls_bn_train_grad_workspace_bytes(rows, c))
+        ws = _bn_train_workspace(nbytes, x.device)
+        _hip.launch("pasnl_cls_bn_train_grad", "bn_train_grad", rows, c, _hip.ptr(x), _hip.ptr(y), _hip.ptr(gamma), _hip.ptr(save_mean),
+                    _hip.ptr(save_rstd), ctx.act, _hip.ptr(grad_y), _hip.ptr(grad_x), _hip.ptr(grad_gamma), _hip.ptr(grad_beta),
+                    _hip.ptr(ws), nbytes)
+        return grad_x, grad_gamma, grad_beta, None, None, None, None, None
+
+
+def _is_relu(activation):
+    return activation in ("relu", torch.relu, torch.nn.functional.relu)
+
+
+def _act_train(x, activation_fn):
+    """_act without the in-place forms: in training the input is another node's saved output"""
+    if activation_fn is None:
+        return x
+    if _is_relu(activation_fn):
+        return torch.relu(x)
+    if activation_fn in ("sigmoid", torch.sigmoid):
+        return torch.sigmoid(x)
+    if activation_fn == "leaky_relu":
+        return torch.nn.functional.leaky_relu(x, 0.2)
+    return activation_fn(x)
+
+
+def _moving_update(moving, batch, decay):
+    """assign_moving_average(zero_debias=False): m <- m - (m - batch) * (1 - decay), in place, outside the graph"""
+    with torch.no_grad():
+        moving.sub_((moving - batch.detach().to(moving.dtype)) * (1.0 - decay))
+
+
+def batch_norm_train_torch(x, gamma, beta, moving_mean, moving_var, decay, activation=None, unbiased=True, dtype=None):
+    """batch_norm_train on torch ops (BN_TRAIN_FUSED = False): centred mean / var(unbiased=False) / normalise, differentiated by
+    torch, and the same moving update.  dtype: the type the statistics (mean, variance, rstd) are TAKEN in -- torch.float64 gives
+    the yardstick the tests measure float32's own noise against; the normalisation itself stays in x's type."""
+    c = x.shape[-1]
+    x2d = x.reshape(-1, c)
+    rows = x2d.shape[0]
+    xs = x2d if dtype is None else x2d.to(dtype)
+    mean = xs.mean(dim=0)
+    var = xs.var(dim=0, unbiased=False)
+    rstd = torch.rsqrt(var + BN_EPS) if dtype is None else 1.0 / torch.sqrt(var + BN_EPS)
+    y = ((x2d - mean.to(x2d.dtype)) * rstd.to(x2d.dtype)) * gamma + beta
+    if moving_mean is not None:
+        _moving_update(moving_mean, mean, decay)
+        _moving_update(moving_var, var * (rows / max(rows - 1, 1)) if unbiased else var, decay)
+    return _act_train(y, activation).reshape(x.shape)
+
+
+def batch_norm_train(x, gamma, beta, moving_mean, moving_var, decay, activation=None, unbiased=True):
+    """Training-mode batch norm over every axis but the last (reference utils/tf_util.py:512-531 with is_training=True):
+    y = activation(gamma * (x - mean) * rstd + beta) with the BATCH's mean and biased variance, rstd = 1 / sqrt(var + 1e-3), and
+    moving_mean / moving_var (both or neither) updated in place, m <- m - (m - batch) * (1 - decay), the variance's `batch`
+    Bessel-corrected when `unbiased` (see _bn_unbiased).  x: any leading shape, the channel last, float32 on the GPU.
+    On csrc/bn_train.hip (ReLU fused, any other activation on torch behind it) with its deterministic backward; carries a grad_fn
+    when x, gamma or beta requires a gradient; under torch.no_grad() it still normalises with the batch's statistics and updates
+    the moving ones.  BN_TRAIN_FUSED = False: batch_norm_train_torch."""
+    decay = _bn_decay_value(decay)
+    if not BN_TRAIN_FUSED:
+        return batch_norm_train_torch(x, gamma, beta, moving_mean, moving_var, decay, activation, unbiased, BN_TRAIN_TORCH_DTYPE)
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise _hip.PasnlError("batch_norm_train takes a float32 tensor on the GPU (no CPU fallback)")
+    if x.numel() == 0:
+        raise ValueError("batch_norm_train: an empty batch has no statistics")
+    c = x.shape[-1]
+    relu = _is_relu(activation)
+    y = _BatchNormTrain.apply(x.reshape(-1, c).contiguous(), gamma.contiguous(), beta.contiguous(), moving_mean, moving_var, decay,
+                              int(relu), bool(unbiased))
+    y = y.reshape(x.shape)
+    return y if relu else _act_train(y, activation)
+
+
+def _dense_train(inputs, num_output_channels, scope, bn, activation_fn, weight_decay, bn_decay, input_pad=0, row_order=None):
+    """A layer in training mode, in the reference's order: convolution (one GEMM with the RAW weights, on the vendor library,
+    differentiated by torch), bias, batch norm with the batch's statistics, activation."""
+    st = store()
+    cin = inputs.shape[-1] - input_pad
+    with variable_scope(scope):
+        if weight_decay is not None:
+            st.decays[st.path("weights")] = float(weight_decay)
+        w, b, gamma, beta, mean, var = st.variables(cin, num_output_channels, bn)
+    if input_pad:  # alignment padding in front of the row, which the reference's tensor does not have
+        inputs = inputs[..., input_pad:]
+    if row_order is not None:  # the producer wrote the cin values of a row in another fixed order
+        w = w[row_order[1]]
+    out = torch.addmm(b, inputs.reshape(-1, cin), w).reshape(*inputs.shape[:-1], num_output_channels)
+    if not bn:
+        return _act_train(out, activation_fn)
+    return batch_norm_train(out, gamma, beta, mean, var, bn_decay, activation_fn, _bn_unbiased(inputs.dim()))
+
+
+class _Dropout(torch.autograd.Function):
+    """pasnl_cls_dropout: no mask is kept, the backward redraws it from the same (seed, stream_id, call)"""
+
+    @staticmethod
+    def forward(ctx, x, keep_prob, seed, stream_id, call):
+        ctx.address = (keep_prob, seed, stream_id, call)
+        return _Dropout.run(x, *ctx.address)
+
+    @staticmethod
+    def run(x, keep_prob, seed, stream_id, call):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        _hip.launch("pasnl_cls_dropout", "dropout", x.numel(), keep_prob, seed, stream_id, call, _hip.ptr(x), _hip.ptr(y))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        return _Dropout.run(grad_y, *ctx.address), None, None, None, None
+
+
+def dropout_stream_id(path):
+    """the 32-bit stream word of a dropout layer: a stable hash of its scope path"""
+    return int.from_bytes(hashlib.sha256(path.encode()).digest()[:4], "little")
 
 
 def _act(x, activation_fn):
@@ -346,10 +624,12 @@ def _dense(inputs, num_output_channels, scope, bn, activation_fn, weight_decay=N
 def conv1d(inputs, num_output_channels, kernel_size, scope, stride=1, padding='SAME', data_format='NHWC',
            use_xavier=True, stddev=1e-3, weight_decay=None, activation_fn="relu", bn=False, bn_decay=None,
            is_training=None):
-    """tf_util.py:52-117, kernel_size 1 only (all the models use)."""
-    _require_inference(is_training)
+    """tf_util.py:52-117, kernel_size 1 only (all the models use).  is_training=True: _dense_train."""
+    training = _training(is_training)
     if kernel_size != 1 or data_format != 'NHWC':
         raise NotImplementedError("conv1d mirror supports kernel_size=1, NHWC")
+    if training:
+        return _dense_train(inputs, num_output_channels, scope, bn, activation_fn, weight_decay, bn_decay)
     return _dense(inputs, num_output_channels, scope, bn, activation_fn, weight_decay)
 
 
@@ -358,15 +638,20 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], paddi
            is_training=None, input_pad=0, row_order=None):
     """tf_util.py:120-185.  [1,1] kernels, and the [1,W] VALID kernel that collapses the whole W axis
     (pointasnl_util.py:275, 337): inputs (B,H,W,C) -> (B,H,1,cout) == one GEMM over the flattened (W,C) window."""
-    _require_inference(is_training)
+    training = _training(is_training)
     kh, kw = kernel_size
     if data_format != 'NHWC' or kh != 1:
         raise NotImplementedError("conv2d mirror supports NHWC, kernel height 1")
     if kw == 1:
+        if training:
+            return _dense_train(inputs, num_output_channels, scope, bn, activation_fn, weight_decay, bn_decay, input_pad=input_pad)
         return _dense(inputs, num_output_channels, scope, bn, activation_fn, weight_decay, input_pad=input_pad)
     if padding != 'VALID' or kw != inputs.shape[2]:
         raise NotImplementedError("conv2d mirror supports [1,1] or the full-width VALID kernel")
     b, h, w, c = inputs.shape
+    if training:  # (b, h, 1, w*c): still rank 4, the statistics over b * h rows
+        return _dense_train(inputs.reshape(b, h, 1, w * c), num_output_channels, scope, bn, activation_fn, weight_decay, bn_decay,
+                            row_order=row_order)
     out = _dense(inputs.reshape(b, h, w * c), num_output_channels, scope, bn, activation_fn, weight_decay, row_order=row_order)
     return out.reshape(b, h, 1, num_output_channels)
 
@@ -374,14 +659,25 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=[1, 1], paddi
 def fully_connected(inputs, num_outputs, scope, use_xavier=True, stddev=1e-3, weight_decay=None,
                     activation_fn="relu", bn=False, bn_decay=None, is_training=None):
     """tf_util.py:327-365"""
-    _require_inference(is_training)
+    if _training(is_training):
+        return _dense_train(inputs, num_outputs, scope, bn, activation_fn, weight_decay, bn_decay)
     return _dense(inputs, num_outputs, scope, bn, activation_fn, weight_decay)
 
 
 def dropout(inputs, is_training, scope, keep_prob=0.5, noise_shape=None):
-    """tf_util.py:594-615: identity at inference."""
-    _require_inference(is_training)
-    return inputs
+    """tf_util.py:594-615: identity at inference; in training tf.nn.dropout(inputs, keep_prob) on pasnl_cls_dropout.  The mask is
+    a function of (the store's seed, a hash of the scope path, the store's dropout_calls counter, the element's index): nothing is
+    stored, the backward redraws it, and setting VariableStore.dropout_calls replays it.  TensorFlow's generator is not reproduced."""
+    if not _training(is_training):
+        return inputs
+    if noise_shape is not None:
+        raise NotImplementedError("dropout mirror supports noise_shape=None only")
+    if not inputs.is_cuda or inputs.dtype != torch.float32:
+        raise _hip.PasnlError("dropout takes a float32 tensor on the GPU (no CPU fallback)")
+    st = store()
+    call = st.dropout_calls & 0xFFFFFFFF
+    st.dropout_calls += 1
+    return _Dropout.apply(inputs, float(keep_prob), st.seed & 0xFFFFFFFFFFFFFFFF, dropout_stream_id(st.path(scope)), call)
 
 
 def l2_loss(t):
